@@ -23,6 +23,16 @@ the upstream gradient dL/dy is a fixed synthetic tensor. The MLP's INT8 gradient
 
 Prints ONE JSON line (rank 0). N=1 by default; N>1 is launched by torch.distributed.run.
 A run whose kernels raised device error flags prints value null and exits with status 3.
+
+A plain run (--mode dp / fwd / sgd without --full) sets up, warms up (--warmup steps, then the
+16-50 untimed steps that a --full run brackets for its breakdown, so both time the same steps
+on the same tables), times --steps steps and prints the line with the headline figure (value,
+ms_per_step). --full adds everything else
+the line can carry, each in a run of its own outside the timed region: the per-phase event
+breakdown and the roofline figures, the INT4 packed-gather bandwidth phase, the MLP INT8
+gradient exchange phase, the CPU baselines and the replica checksum. --dump-outputs DIR
+writes what the last timed step left (the forward output, the updated rows, the scales) as
+DIR/<name>.npy: the same arguments give the same inputs, so two builds compare array by array.
 """
 from __future__ import annotations
 
@@ -58,6 +68,13 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="dp / fwd / sgd modes: besides the timed steps, run the per-phase breakdown and roofline, "
+                        "the INT4 gather phase (--gather-batch), the MLP exchange phase (--mlp-iters), the CPU "
+                        "baselines (--cpu-baseline) and the replica checksum; without it the line carries null there")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="dp / fwd / sgd modes: after the timed steps write what the last one left (forward output, "
+                        "updated rows, scales) as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     p.add_argument("--config", default="terabyte", choices=sorted(CONFIGS))
     p.add_argument("--mode", default="dp", choices=["dp", "fwd", "sgd", "dropin-sgd", "dropin-dp", "dlrm"],
                    help="dp: data-parallel QAT step; fwd: forward only; sgd: forward + fused sparse SGD; "
@@ -94,11 +111,11 @@ def parse(argv=None):
     p.add_argument("--index-dist", default="uniform", choices=["uniform", "zipf"])
     p.add_argument("--num-batches", type=int, default=8, help="distinct resident batches cycled")
     p.add_argument("--gather-batch", type=int, default=65536,
-                   help="bags per table for the INT4 packed-gather bandwidth phase (0 = skip)")
+                   help="--full: bags per table for the INT4 packed-gather bandwidth phase (0 = skip)")
     p.add_argument("--gather-iters", type=int, default=50)
     p.add_argument("--mlp-iters", type=int, default=50,
-                   help="iterations of the MLP INT8 gradient exchange phase (0 = skip)")
-    p.add_argument("--cpu-baseline", type=int, default=1)
+                   help="--full: iterations of the MLP INT8 gradient exchange phase (0 = skip)")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="--full: run the CPU baselines (0 = skip)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline sample")
     p.add_argument("--seed", type=int, default=123)
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -126,7 +143,7 @@ def parse(argv=None):
     p.add_argument("--two-launch-local", action="store_true",
                    help="N=1: coalesce + dqrm_apply_local as two launches (not dqrm_emb_bwd_apply_local)")
     p.add_argument("--sample-every", type=int, default=0,
-                   help="also bracket the dominant kernel with HIP events on every k-th TIMED step "
+                   help="--full: also bracket the dominant kernel with HIP events on every k-th TIMED step "
                         "(0 = never: the roofline is timed on the untimed breakdown pass's >= 16 "
                         "bracketed launches, so no event work sits inside the timed region)")
     p.add_argument("--traffic-profile", default=None,
@@ -257,6 +274,48 @@ def phase_names(mode, use_packed, fused, one_launch=False, next_fwd=False, coll_
     return [fwd, "bwd_coalesce"] + (["apply_local"] if fused else ["grad_quant_pack", "apply_sparse_update"])
 
 
+DUMP_ARRAY_BYTES = 20 << 20  # per dumped array; three sampled arrays + the [T] vectors stay under 64 MB
+
+
+def sample_rows(x, seed, cap=DUMP_ARRAY_BYTES):
+    """x [N, D] on the device -> float32 numpy [k, D]: every row when they fit in cap bytes,
+    else the k rows a RandomState(seed) draws (sorted; the same rows for the same shape)."""
+    n, d = x.shape
+    k = max(1, cap // (d * 4))
+    if n > k:
+        pick = np.sort(np.random.RandomState(seed).randint(0, n, k))
+        x = x[torch.from_numpy(pick).to(x.device)]
+    return x.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(path, seed, ts, y, last, ex):
+    """Write what the last timed step left for its caller as path/<name>.npy (float32):
+    y            the forward output the step returned, [T * B, D] (bags of table 0 first)
+    W_updated    the table rows the step's batch addressed, after its update, [T * B, D] in the
+                 batch's lookup order (--mode fwd leaves them as initialised)
+    W_sample     rows drawn from the whole row slab by a fixed seed (rows no step touched included)
+    table_absmax, table_scale   [T]: each table's max|W| and its INT4 scale as the step left them
+    grad_scale   [T]: the step's rank-averaged gradient scale (dp mode)
+    Arrays above DUMP_ARRAY_BYTES are cut to a seeded row sample (sample_rows)."""
+    os.makedirs(path, exist_ok=True)
+    T, D = ts.T, ts.D
+    out = {"y": sample_rows(y.view(-1, D), seed + 1),
+           "W_sample": sample_rows(ts.W, seed + 2),
+           "table_absmax": ts.tmax.cpu().numpy(), "table_scale": ts.scale.cpu().numpy()}
+    base = torch.tensor(ts.row_base, dtype=torch.int64, device=ts.W.device).view(T, 1)
+    rows = (last.idx.view(T, -1) + base).view(-1)
+    k = max(1, DUMP_ARRAY_BYTES // (D * 4))
+    if rows.numel() > k:  # sample the lookups, not the gathered rows
+        pick = np.sort(np.random.RandomState(seed + 3).randint(0, rows.numel(), k))
+        rows = rows[torch.from_numpy(pick).to(rows.device)]
+    out["W_updated"] = ts.W[rows].cpu().numpy()
+    if getattr(ex, "s_avg", None) is not None:
+        out["grad_scale"] = ex.s_avg.cpu().numpy()
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return sorted(out)
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -270,6 +329,9 @@ def main():
         sys.exit(2)
     if a.graph and world > 1:
         print("--graph runs at N=1 only (the collectives stay eager)", file=sys.stderr)
+        sys.exit(2)
+    if a.dump_outputs and (a.emulate_ranks > 1 or a.mode not in ("dp", "fwd", "sgd")):
+        print("--dump-outputs writes the dp / fwd / sgd step's outputs", file=sys.stderr)
         sys.exit(2)
     if a.scaling == "strong" and a.global_batch <= 0:
         a.global_batch = a.batch_per_gpu  # the batch is the global one, split over the ranks
@@ -309,8 +371,8 @@ def main():
     B = B_global // world
 
     t0 = time.time()
-    ts = dq.EmbeddingTableSet(rows, D, device=dev, packed=a.gather_batch > 0 or a.use_packed, init="uniform",
-                              seed=a.seed)
+    ts = dq.EmbeddingTableSet(rows, D, device=dev, packed=(a.full and a.gather_batch > 0) or a.use_packed,
+                              init="uniform", seed=a.seed)
     batches = make_batches(rows, B_global, rank, world, a.num_batches, a.seed, a.index_dist, dev)
     dy = torch.randn(T, B, D, device=dev, generator=torch.Generator(device=dev).manual_seed(a.seed + rank)) * 0.05
     y = torch.empty(T, B, D, device=dev)
@@ -451,15 +513,21 @@ def main():
     for i in range(a.warmup):
         step(i)
     torch.cuda.synchronize()
-    # per-phase breakdown (untimed, eager): every phase bracketed by events; picks the dominant.
+    # --full: per-phase breakdown (untimed, eager): every phase bracketed by events; picks the dominant.
     # Periodic mode: steady-state steps only; the refresh (every P steps) is timed apart.
+    # A plain run takes the same nb steps unbracketed: the timed region then starts from the same
+    # tables and resident batch in both kinds of run (their outputs are equal) and from a device
+    # that has been stepping for as long (same-box A/B: 0.5-1% slower per step without them).
     nb = max(16, min(50, a.steps))  # >= 16 bracketed launches of every phase
-    bev = [timed_events(len(names)) for _ in range(nb)]
+    bev = [timed_events(len(names)) for _ in range(nb)] if a.full else None
     for i in range(nb):
-        step(i, bev[i], refresh=a.scale_period <= 0, split=True)
+        if a.full:
+            step(i, bev[i], refresh=a.scale_period <= 0, split=True)
+        else:
+            step(i, refresh=a.scale_period <= 0)
     torch.cuda.synchronize()
     refresh_ms = None
-    if a.use_packed:  # new scales from the |W| hierarchy + INT4 repack of every table whose scale moved
+    if a.full and a.use_packed:  # new scales from the |W| hierarchy + INT4 repack of every table whose scale moved
         rev = timed_events(3)
         for e0, e1 in rev:
             ts.pscale.fill_(float("nan"))
@@ -468,10 +536,12 @@ def main():
             e1.record()
         torch.cuda.synchronize()
         refresh_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in rev]))
-    kms = {n: float(np.mean([bev[i][j][0].elapsed_time(bev[i][j][1]) for i in range(nb)]))
-           for j, n in enumerate(names)}
-    dom = max(kms, key=kms.get)
-    dj = names.index(dom)
+    kms = dom = dj = None
+    if a.full:
+        kms = {n: float(np.mean([bev[i][j][0].elapsed_time(bev[i][j][1]) for i in range(nb)]))
+               for j, n in enumerate(names)}
+        dom = max(kms, key=kms.get)
+        dj = names.index(dom)
 
     graphs = None
     gs = 1
@@ -524,7 +594,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     every = a.sample_every
-    sampled = ([] if graphs is not None or lib_exchange or every <= 0 else
+    sampled = ([] if not a.full or graphs is not None or lib_exchange or every <= 0 else
                [i for i in range(a.steps) if i % every == 0])
     evs = {i: timed_events(len(names)) for i in sampled}
     t_start = time.perf_counter()
@@ -538,39 +608,45 @@ def main():
         e = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
-    dom_ms = (float(np.mean([evs[i][dj][0].elapsed_time(evs[i][dj][1]) for i in sampled])) if sampled
-              else kms[dom])  # the breakdown pass's average over its nb >= 16 bracketed launches
-
-    # algorithmic bytes per launch; distinct rows of the last step's batch
-    if ex is not None:
-        U = int(ex.ws.ucount.sum().item())
-    else:
-        P = batches[(a.warmup + a.steps - 1) % len(batches)].idx.view(T, -1)
-        U = int(sum(torch.unique(P[t]).numel() for t in range(T)))
-    alg = alg_bytes(dom, T, B, D, U, world, pool1=True, repack=repack)
-    step_alg = sum(alg_bytes(n, T, B, D, U, world, pool1=True, repack=repack) for n in names)
-    achieved = alg / (dom_ms * 1e-3) / 1e9
     err = ts.read_errors()
+    dumped = None
+    if a.dump_outputs and rank == 0:  # before any later phase touches the tables' scales
+        dumped = dump_outputs(a.dump_outputs, a.seed, ts, y, batches[(a.warmup + a.steps - 1) % len(batches)], ex)
 
-    gather = gather_phase(a, ts, rows, T, D, dev) if a.gather_batch > 0 else None
-    mlp = dense_phase(a, dev, world, rank, coll) if a.mlp_iters > 0 else None
+    dom_ms = alg = step_alg = achieved = None
+    gather = mlp = cpu = cpu_c = replicas_match = None
+    if a.full:
+        dom_ms = (float(np.mean([evs[i][dj][0].elapsed_time(evs[i][dj][1]) for i in sampled])) if sampled
+                  else kms[dom])  # the breakdown pass's average over its nb >= 16 bracketed launches
 
-    cpu = cpu_c = None  # the CPU baselines are N=1 figures: a single-rank run only
-    if world == 1 and a.cpu_baseline:
-        cpu = cpu_baseline_torch(a, B)
-        cpu_c = cpu_baseline_oracle(a, min(B, 2048))
+        # algorithmic bytes per launch; distinct rows of the last step's batch
+        if ex is not None:
+            U = int(ex.ws.ucount.sum().item())
+        else:
+            P = batches[(a.warmup + a.steps - 1) % len(batches)].idx.view(T, -1)
+            U = int(sum(torch.unique(P[t]).numel() for t in range(T)))
+        alg = alg_bytes(dom, T, B, D, U, world, pool1=True, repack=repack)
+        step_alg = sum(alg_bytes(n, T, B, D, U, world, pool1=True, repack=repack) for n in names)
+        achieved = alg / (dom_ms * 1e-3) / 1e9
 
-    # replicas must stay bit-identical (deterministic kernels, same exchanged data): compare a
-    # checksum of every rank's W bit patterns and table maxima (outside the timed region)
-    wbits = ts.W.view(-1).view(torch.int32)
-    wsum = sum(c.sum(dtype=torch.int64) for c in wbits.split(1 << 26))  # 512 MB int64 temporaries
-    cs = torch.stack([wsum, ts.tmax.view(torch.int32).sum(dtype=torch.int64)])
-    if world > 1:
-        allcs = [torch.zeros_like(cs) for _ in range(world)]
-        dist.all_gather(allcs, cs)
-        replicas_match = all(torch.equal(allcs[0], c) for c in allcs)
-    else:
-        replicas_match = True
+        gather = gather_phase(a, ts, rows, T, D, dev) if a.gather_batch > 0 else None
+        mlp = dense_phase(a, dev, world, rank, coll) if a.mlp_iters > 0 else None
+
+        if world == 1 and a.cpu_baseline:  # the CPU baselines are N=1 figures: a single-rank run only
+            cpu = cpu_baseline_torch(a, B)
+            cpu_c = cpu_baseline_oracle(a, min(B, 2048))
+
+        # replicas must stay bit-identical (deterministic kernels, same exchanged data): compare a
+        # checksum of every rank's W bit patterns and table maxima (outside the timed region)
+        wbits = ts.W.view(-1).view(torch.int32)
+        wsum = sum(c.sum(dtype=torch.int64) for c in wbits.split(1 << 26))  # 512 MB int64 temporaries
+        cs = torch.stack([wsum, ts.tmax.view(torch.int32).sum(dtype=torch.int64)])
+        if world > 1:
+            allcs = [torch.zeros_like(cs) for _ in range(world)]
+            dist.all_gather(allcs, cs)
+            replicas_match = all(torch.equal(allcs[0], c) for c in allcs)
+        else:
+            replicas_match = True
     n1_update = ("SGD of step i + forward of step i+1 (dqrm_emb_bwd_sgd_fwd)" if a.mode == "sgd" and next_fwd else
                  None if a.mode != "dp" or world > 1 else
                  "coalesce + quant-pack + payload apply with the next forward (RCCL at world size 1)"
@@ -582,9 +658,11 @@ def main():
     workload = {"config": a.config, "mode": a.mode, "batch_per_gpu": B, "n1_update": n1_update,
                 "index_dist": a.index_dist}
     # (the forced-collectives N > 1 form is profiled under its own tag, e.g. r5_tbforced)
-    prof = a.traffic_profile or latest_profile(PROFILE_TAG[a.config] + ("forced" if coll and world == 1 else ""))
-    traffic = pmc_traffic(prof, dom + ("_fin" if dom == "apply_sparse_update_fwd" and coll_form == "fin_fwd" else ""),
-                          D, workload)
+    traffic = None
+    if a.full:
+        prof = a.traffic_profile or latest_profile(PROFILE_TAG[a.config] + ("forced" if coll and world == 1 else ""))
+        traffic = pmc_traffic(prof, dom + ("_fin" if dom == "apply_sparse_update_fwd" and coll_form == "fin_fwd"
+                                           else ""), D, workload)
     med_us = traffic["profiled_median_us"] if traffic else None
     if rank == 0:
         value = B_global * a.steps / elapsed
@@ -629,7 +707,9 @@ def main():
                 "n1_update": n1_update,
                 "parallelism": f"dp{world} (tables replicated)",
             },
-            "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "full": a.full,  # false: the figures below that take runs of their own are null (--full)
+            "roofline": None if not a.full else {
+                         "kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic["bytes"] if traffic else None, "traffic_unit": "bytes/launch",
                          "traffic_src": traffic,
@@ -641,12 +721,14 @@ def main():
                                                  if med_us else None),
                          "workload_profiled": workload},
             # the whole step against the same peak: every phase's algorithmic bytes / step time
-            "step_roofline": {"alg_bytes_per_step": step_alg,
+            "step_roofline": None if not a.full else {
+                              "alg_bytes_per_step": step_alg,
                               "achieved": round(step_alg / (elapsed / a.steps) / 1e9, 1),
                               "frac": round(step_alg / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS, 4),
                               "phases": names},
-            "kernels_ms": {k: round(v, 5) for k, v in kms.items()},
-            "kernels_ms_note": "untimed eager breakdown pass, every phase bracketed by events; " + (
+            "kernels_ms": {k: round(v, 5) for k, v in kms.items()} if a.full else None,
+            "kernels_ms_note": None if not a.full else "untimed eager breakdown pass, every phase bracketed by "
+                               "events; " + (
                 "bwd_sgd_fwd = the SGD of this step's batch, then the next batch's forward, one workgroup per "
                 "table (one launch when the small-batch kernel runs)" if a.mode == "sgd" and next_fwd
                 else "bwd_apply_fwd_local is ONE launch per step: coalesce, quantize, update and the |W| hierarchy of "
@@ -669,7 +751,7 @@ def main():
             "scale_refresh_note": ("full INT4 repack of all tables (worst case: every scale moved), once per "
                                    f"{a.scale_period} steps" if refresh_ms is not None else None),
             "launch_share": (round(max(0.0, 1.0 - sum(kms.values()) / (elapsed / a.steps * 1e3)), 4)
-                             if not a.graph else None),
+                             if a.full and not a.graph else None),
             "collectives": colls,
             "int4_gather": gather,
             "mlp_grad_exchange": mlp,
@@ -678,6 +760,7 @@ def main():
             "device_errors": err,
             "replicas_bit_identical": replicas_match,
             "setup_s": round(setup_s, 1),
+            "outputs_dumped": dumped,
         }
         print(json.dumps(line), flush=True)
     if coll:

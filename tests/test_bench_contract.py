@@ -98,6 +98,57 @@ def test_phase_names(bench):
                                                           + bench.alg_bytes("emb_fwd", T, B, D, U))
 
 
+def test_full_and_dump_outputs_are_off_by_default(bench):
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_sample_rows_is_seeded_and_bounded(bench):
+    import numpy as np
+    import torch
+
+    x = torch.arange(1000 * 8, dtype=torch.float32).view(1000, 8)
+    whole = bench.sample_rows(x, 5, cap=1000 * 8 * 4)
+    assert whole.dtype == np.float32 and np.array_equal(whole, x.numpy())
+    s1, s2 = bench.sample_rows(x, 5, cap=4096), bench.sample_rows(x, 5, cap=4096)
+    assert s1.shape == (128, 8) and s1.nbytes <= 4096 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1[:, 0]) >= 0) and np.all(s1[:, 0] % 8 == 0)  # whole rows, in row order
+    assert not np.array_equal(s1, bench.sample_rows(x, 6, cap=4096))
+
+
+def test_dump_outputs_writes_float32_arrays(bench, tmp_path):
+    """dump_outputs on a host stand-in of the table set: y and the rows the last batch addressed
+    whole, the [T] vectors, all float32, the same files from the same state."""
+    import types
+
+    import numpy as np
+    import torch
+
+    rows, D, B = [5, 40, 300], 8, 16
+    g = torch.Generator().manual_seed(3)
+    W = torch.randn(sum(rows), D, generator=g)
+    ts = types.SimpleNamespace(T=3, D=D, W=W, row_base=[0, 5, 45], tmax=torch.rand(3, generator=g),
+                               scale=torch.rand(3, generator=g))
+    idx = torch.stack([torch.randint(0, n, (B,), generator=g) for n in rows])
+    last = types.SimpleNamespace(idx=idx.view(-1))
+    y = torch.randn(3, B, D, generator=g)
+    ex = types.SimpleNamespace(s_avg=torch.rand(3, generator=g))
+    names = bench.dump_outputs(str(tmp_path / "a"), 123, ts, y, last, ex)
+    assert names == ["W_sample", "W_updated", "grad_scale", "table_absmax", "table_scale", "y"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["y"], y.view(-1, D).numpy()) and np.array_equal(got["W_sample"], W.numpy())
+    want = torch.cat([W[ts.row_base[t] + idx[t]] for t in range(3)]).numpy()
+    assert np.array_equal(got["W_updated"], want)
+    assert np.array_equal(got["grad_scale"], ex.s_avg.numpy())
+    assert bench.dump_outputs(str(tmp_path / "b"), 123, ts, y, last, None) == [n for n in names if n != "grad_scale"]
+    for n in names:
+        if n != "grad_scale":
+            assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+
+
 @pytest.mark.parametrize("mode", ["dp", "sgd", "fwd"])
 def test_cpu_baseline_torch_runs(bench, mode):
     """The PyTorch-CPU restatement of the reference step runs on small tables and reports

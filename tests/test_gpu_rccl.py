@@ -127,7 +127,7 @@ def test_bench_launcher_rccl_world1():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--force-collectives", "--config", "kaggle", "--steps", "20", "--warmup", "5",
-           "--cpu-baseline", "0", "--gather-batch", "0", "--mlp-iters", "5"]
+           "--full", "--cpu-baseline", "0", "--gather-batch", "0", "--mlp-iters", "5"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -153,7 +153,7 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--dist-backend", "gloo", "--config", "kaggle", "--steps", "10", "--warmup", "3",
-           "--cpu-baseline", "0", "--gather-batch", "0", "--mlp-iters", "0"]
+           "--full", "--cpu-baseline", "0", "--gather-batch", "0", "--mlp-iters", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

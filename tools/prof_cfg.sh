@@ -7,7 +7,7 @@ TAG=$1
 CFG=$2
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-ARGS="--config $CFG --steps 20 --warmup 5 --cpu-baseline 0 --gather-iters 20 --mlp-iters 10 ${EXTRA:-}"
+ARGS="--config $CFG --steps 20 --warmup 5 --full --cpu-baseline 0 --gather-iters 20 --mlp-iters 10 ${EXTRA:-}"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_${TAG}_trace -o tb --output-format csv -- python3 $R/bench.py $ARGS > $R/gpurun_out/prof_${TAG}_trace.log 2>&1 && \
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d $R/gpurun_out/prof_${TAG}_fetch -o tb --output-format csv -- python3 $R/bench.py $ARGS > $R/gpurun_out/prof_${TAG}_fetch.log 2>&1 && \
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -d $R/gpurun_out/prof_${TAG}_write -o tb --output-format csv -- python3 $R/bench.py $ARGS > $R/gpurun_out/prof_${TAG}_write.log 2>&1 && \
