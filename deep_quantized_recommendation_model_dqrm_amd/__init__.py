@@ -2,6 +2,7 @@
 
 Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM):
   * ``quant_modules_not_quantize_grad.QuantEmbeddingBagTwo``  (INT4 fake-quant EmbeddingBag)
+  * ``quant_modules_not_quantize_grad.QuantLinear``            (INT4 fake-quant MLP layer, f32 MFMA)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
@@ -15,6 +16,7 @@ from .comm import MultiSetExchange, SparseGradExchange, get_my_slice, payload_by
 from .dense import DenseGradExchange
 from . import quant_modules_not_quantize_grad, sgd_quantized_gradients, sgd_quantized_gradients_parallel_comm
 from .quant_modules_not_quantize_grad import QuantEmbeddingBagCollection, QuantEmbeddingBagTwo
+from .linear import QuantLinear
 from . import quantized_ops
 
 __all__ = [
@@ -33,6 +35,7 @@ __all__ = [
     "DenseGradExchange",
     "QuantEmbeddingBagTwo",
     "QuantEmbeddingBagCollection",
+    "QuantLinear",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

@@ -56,7 +56,7 @@ DQRM_WIRE_F16 = 1
 DQRM_WIRE_I32 = 2
 DQRM_WIRE_F32 = 3
 
-DQRM_ABI_VERSION = 11  # include/dqrm.h
+DQRM_ABI_VERSION = 12  # include/dqrm.h
 DQRM_PRESUM_MAX_LOOKUPS = 2048
 
 # every symbol include/dqrm.h declares (checked by tests/test_abi.py)
@@ -95,6 +95,9 @@ EXPORTED_SYMBOLS = (
     "dqrm_dense_grad_quant",
     "dqrm_dense_grad_decode",
     "dqrm_dense_update",
+    "dqrm_linear_wquant",
+    "dqrm_linear_fwd",
+    "dqrm_linear_bwd",
     "dqrm_criteo_unpack",
     "dqrm_rowwise_row_bytes",
     "dqrm_rowwise_prepack",
@@ -180,6 +183,24 @@ class DenseSet(C.Structure):
     ]
 
 
+class Linear(C.Structure):
+    """Mirror of ``dqrm_linear`` (include/dqrm.h)."""
+
+    _fields_ = [
+        ("in_features", C.c_int32),
+        ("out_features", C.c_int32),
+        ("weight_bit", C.c_int32),
+        ("bias_bit", C.c_int32),
+        ("per_channel", C.c_int32),
+        ("reserved", C.c_int32),
+        ("weight", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("weight_integer", C.c_void_p),
+        ("bias_integer", C.c_void_p),
+        ("scale", C.c_void_p),
+    ]
+
+
 class Exchange(C.Structure):
     """Mirror of ``dqrm_exchange`` (include/dqrm.h): one rank's exchange buffers."""
 
@@ -232,6 +253,7 @@ def load(path: str | None = None) -> C.CDLL:
     TS = C.POINTER(TableSet)
     BA = C.POINTER(Batch)
     DS = C.POINTER(DenseSet)
+    LN = C.POINTER(Linear)
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -315,6 +337,9 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_dense_grad_quant": (C.c_int, [DS, C.c_int, P, C.c_int, P, C.c_int, P, P]),
         "dqrm_dense_grad_decode": (C.c_int, [DS, P, C.c_int, C.c_int, P]),
         "dqrm_dense_update": (C.c_int, [DS, P, C.c_float, P]),
+        "dqrm_linear_wquant": (C.c_int, [LN, P]),
+        "dqrm_linear_fwd": (C.c_int, [LN, C.c_int, P, C.c_int64, P, P]),
+        "dqrm_linear_bwd": (C.c_int, [LN, C.c_int, P, P, C.c_int64, P, P, P, P]),
         "dqrm_criteo_unpack": (C.c_int, [P, C.c_int64, C.c_int32, P, P, P, P, P]),
         "dqrm_rowwise_row_bytes": (C.c_size_t, [C.c_int, C.c_int]),
         "dqrm_rowwise_prepack": (C.c_int, [C.c_int, P, C.c_int64, C.c_int, P, P]),

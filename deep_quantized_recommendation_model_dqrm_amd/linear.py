@@ -1,0 +1,194 @@
+"""Drop-in for the reference's ``QuantLinear`` (quantization_supp/
+quant_modules_not_quantize_grad.py:20-211), backed by libdqrm's f32-MFMA kernels
+(csrc/dqrm_linear.hip; no CPU fallback).
+
+The reference's drivers build every bot_l / top_l layer as
+``QuantLinear(weight_bit, bias_bit, full_precision_flag, per_channel, quantize_activation)``
+followed by ``set_param(nn.Linear)`` and call it as ``x, prev = layer(x, prev)``
+(dlrm_s_pytorch_comm_grad.py:279-343, :574-612). This module keeps that constructor, the
+buffer names and state-dict keys of ``set_param`` (:70-97), ``__repr__`` (:64-68) and the
+``(y, None)`` return of the weight-only forward (:209, :211):
+
+  * quantized forward (3 launches with per_channel, 4 without): dqrm_linear_wquant refreshes
+    ``fc_scaling_factor``, ``weight_integer`` and ``bias_integer`` from the current weights
+    (symmetric, the bias with the weight's scale), then dqrm_linear_fwd computes
+    ``(x @ weight_integer.T + bias_integer) * fc_scaling_factor``;
+  * full_precision_flag: ``x @ weight.T + bias`` on the same kernel;
+  * backward (2 launches, 1 for a layer whose input needs no gradient): the STE of
+    SymmetricQuantFunction (quant_utils.py:349-363), dqrm_linear_bwd.
+
+Every sum is an f32 fmaf chain in ascending index (include/dqrm.h), so a row's output does not
+depend on the batch it is part of and every data-parallel replica computes the same bits.
+
+Not built: ``QuantAct`` / activation quantization (``quantize_activation=True``, a
+``prev_act_scaling_factor``) and asymmetric weights (the reference raises there too).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch import nn
+from torch.nn import Parameter
+
+from . import _lib as L
+from .tables import _stream_handle
+
+
+def _check_input(x: torch.Tensor, layer: "QuantLinear") -> None:
+    w = layer.weight
+    if x.device.type != "cuda" or w.device.type != "cuda":
+        raise L.DQRMError(f"QuantLinear runs on libdqrm's HIP kernels: input and layer must be on a GPU "
+                          f"(got {x.device} / {w.device}); there is no CPU path")
+    if x.device != w.device:
+        raise ValueError(f"input on {x.device} but the layer on {w.device}")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != layer.in_features or not x.is_contiguous():
+        raise ValueError(f"QuantLinear needs a contiguous float32 [B, {layer.in_features}] input "
+                         f"(got {x.dtype} {tuple(x.shape)}, contiguous={x.is_contiguous()})")
+
+
+class _LinearFn(torch.autograd.Function):
+    """Autograd bridge over dqrm_linear_wquant / _fwd / _bwd. The backward reads the integers and
+    scale the layer's latest forward wrote (the same ones unless the weights changed in between)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner, quantized):
+        lib, c, st = owner._lib, owner._c_struct(), _stream_handle()
+        if quantized:
+            L.check(lib.dqrm_linear_wquant(C.byref(c), st), "dqrm_linear_wquant")
+        y = torch.empty((x.shape[0], owner.out_features), dtype=torch.float32, device=x.device)
+        L.check(lib.dqrm_linear_fwd(C.byref(c), int(quantized), x.data_ptr(), x.shape[0], y.data_ptr(), st),
+                "dqrm_linear_fwd")
+        ctx.save_for_backward(x)
+        ctx.owner = owner
+        ctx.quantized = quantized
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        owner = ctx.owner
+        dy = dy.contiguous()
+        B = x.shape[0]
+        dw = torch.empty_like(owner.weight)
+        db = torch.empty_like(owner.bias)
+        if B == 0:
+            return (torch.empty_like(x) if ctx.needs_input_grad[0] else None), dw.zero_(), db.zero_(), None, None
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        L.check(owner._lib.dqrm_linear_bwd(C.byref(owner._c_struct()), int(ctx.quantized), x.data_ptr(),
+                                           dy.data_ptr(), B, None if dx is None else dx.data_ptr(),
+                                           dw.data_ptr(), db.data_ptr(), _stream_handle()),
+                "dqrm_linear_bwd")
+        return dx, dw, db, None, None
+
+
+class QuantLinear(nn.Module):
+    """quant_modules_not_quantize_grad.py:20-211 on libdqrm: constructor arguments, defaults,
+    buffers and forward signature of the reference."""
+
+    def __init__(self, weight_bit=4, bias_bit=None, full_precision_flag=False, quant_mode="symmetric",
+                 per_channel=False, fix_flag=False, weight_percentile=0, quantize_activation=False):
+        super().__init__()
+        self.full_precision_flag = full_precision_flag
+        self.weight_bit = weight_bit
+        self.quant_mode = quant_mode
+        self.per_channel = per_channel
+        self.fix_flag = fix_flag
+        self.weight_percentile = weight_percentile
+        self.bias_bit = bias_bit
+        self.quantize_bias = bias_bit is not None
+        self.counter = 0
+        self.quantize_activation = quantize_activation
+        self.__dict__["_c"] = None  # (key, L.Linear): rebuilt when a tensor's storage moves
+
+    def __repr__(self):
+        s = super().__repr__()
+        return "(" + s + " weight_bit={}, full_precision_flag={}, quantize_fn={})".format(
+            self.weight_bit, self.full_precision_flag, self.quant_mode)
+
+    def set_param(self, linear):
+        """q_m_n_q_g.py:70-97: take a Linear layer's weights; the buffers live where they do."""
+        if getattr(linear, "bias", None) is None:
+            raise ValueError("QuantLinear.set_param needs a Linear layer with a bias (the reference "
+                             "quantizes it with the weight's scale)")
+        self.in_features = linear.in_features
+        self.out_features = linear.out_features
+        dev = linear.weight.device
+        self.register_buffer("fc_scaling_factor", torch.zeros(self.out_features, device=dev))
+        self.register_buffer("correct_output_scale", torch.ones(self.out_features, device=dev))
+        self.weight = Parameter(linear.weight.data.clone().float().contiguous())
+        self.register_buffer("weight_integer", torch.zeros_like(self.weight), persistent=False)
+        self.register_buffer("bias_integer", torch.zeros_like(linear.bias, dtype=torch.float32), persistent=False)
+        self.register_buffer("weight_scaling_factor", torch.zeros(self.out_features, device=dev))
+        self.register_buffer("error_compensation_weight", torch.zeros_like(self.weight), persistent=False)
+        self.bias = Parameter(linear.bias.data.clone().float().contiguous())
+        self.register_buffer("bias_scaling_factor", torch.zeros(self.out_features, device=dev))
+        self.register_buffer("error_compensation_bias", torch.zeros_like(self.bias), persistent=False)
+        self.__dict__["_c"] = None
+
+    def fix(self):
+        self.fix_flag = True
+
+    def unfix(self):
+        self.fix_flag = False
+
+    # ------------------------------------------------------------ the C view of the layer
+    @property
+    def _lib(self):
+        return L.load()
+
+    def _c_struct(self) -> L.Linear:
+        ts = (self.weight, self.bias, self.weight_integer, self.bias_integer, self.fc_scaling_factor)
+        key = tuple(t.data_ptr() for t in ts) + (self.weight_bit, self.bias_bit, bool(self.per_channel))
+        ent = self.__dict__["_c"]
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        for t in ts:
+            if t.device != self.weight.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("QuantLinear needs contiguous float32 parameters and buffers on one device")
+        c = L.Linear()
+        c.in_features, c.out_features = self.in_features, self.out_features
+        c.weight_bit = int(self.weight_bit)
+        c.bias_bit = int(self.bias_bit) if self.bias_bit is not None else 0
+        c.per_channel = int(bool(self.per_channel))
+        c.weight, c.bias, c.weight_integer, c.bias_integer, c.scale = key[:5]
+        self.__dict__["_c"] = (key, c)
+        return c
+
+    def _scale_buffer(self) -> None:
+        """fc_scaling_factor as the reference leaves it: [out_features] with per_channel, [1]
+        without (q_m_n_q_g.py:124-144), on the weight's device."""
+        n = self.out_features if self.per_channel else 1
+        s = self.fc_scaling_factor
+        if s.numel() != n or s.device != self.weight.device:
+            self.fc_scaling_factor = torch.zeros(n, dtype=torch.float32, device=self.weight.device)
+
+    # ------------------------------------------------------------ forward
+    def forward(self, x, prev_act_scaling_factor=None):
+        """(y, None), as the reference's weight-only QuantLinear returns."""
+        if type(x) is tuple:
+            prev_act_scaling_factor = x[1]
+            x = x[0]
+        quantized = not self.full_precision_flag
+        if quantized:
+            if self.quant_mode == "asymmetric":
+                raise Exception("For weight, we only support symmetric quantization.")
+            if self.quant_mode != "symmetric":
+                raise ValueError("unknown quant mode: {}".format(self.quant_mode))
+            if self.quantize_activation or prev_act_scaling_factor is not None:
+                raise NotImplementedError("activation quantization (QuantAct, quantize_activation=True, "
+                                          "prev_act_scaling_factor) is not built")
+            if self.bias_bit is None:
+                raise TypeError("QuantLinear quantizes its bias: bias_bit must be an int")
+        if "weight" not in self._parameters:
+            raise RuntimeError("QuantLinear.set_param(linear) has not been called")
+        _check_input(x, self)
+        if quantized:
+            self._scale_buffer()
+        if x.device.index != torch.cuda.current_device():
+            with torch.cuda.device(x.device):
+                return _LinearFn.apply(x, self.weight, self.bias, self, quantized), None
+        return _LinearFn.apply(x, self.weight, self.bias, self, quantized), None
+
+
+__all__ = ["QuantLinear"]

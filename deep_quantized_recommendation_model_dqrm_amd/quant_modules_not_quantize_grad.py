@@ -21,6 +21,9 @@ state-dict keys (:258-280, :288), and its semantics (:317-398):
       grad_mode="dp"        -> the gradient is kept on device for
                                sgd_quantized_gradients_parallel_comm.grad_update_parallel_comm.
 
+``QuantLinear`` (the MLP layers, :20-211) lives in ``linear.py`` and is re-exported here, where
+the reference's drivers import it from.
+
 ``QuantEmbeddingBagCollection`` is the fused T-table form used to replace the per-table
 loop of DLRM_Net.apply_emb (dlrm_s_pytorch_single_gpu.py:609-674): one launch per step for
 all tables instead of 26.
@@ -36,6 +39,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from .linear import QuantLinear  # the reference defines it in this module (q_m_n_q_g.py:20-211)
 from .tables import EmbeddingTableSet, LookupBatch
 
 
@@ -626,6 +630,6 @@ class QuantEmbeddingBagCollection(_QuantEmbeddingBase):
         return out
 
 
-__all__ = ["QuantEmbeddingBagTwo", "QuantEmbeddingBagCollection", "set_default_grad_mode", "set_sparse_grad_form",
+__all__ = ["QuantLinear", "QuantEmbeddingBagTwo", "QuantEmbeddingBagCollection", "set_default_grad_mode", "set_sparse_grad_form",
            "set_fused_optimizer_step",
            "set_error_check_interval", "set_pooling_one_inputs", "consolidate_tables", "can_consolidate"]

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DQRM_ABI_VERSION 11 /* 2: dqrm_table_set.bdirty, dqrm_set_apply_kernel, dqrm_apply_local;
+#define DQRM_ABI_VERSION 12 /* 2: dqrm_table_set.bdirty, dqrm_set_apply_kernel, dqrm_apply_local;
                                3: backward workspace (dqrm_bwd_workspace_bytes), no per-slot key cap;
                                4: dqrm_table_set.sync (in-launch hierarchy finalize), padded flags;
                                5: dqrm_emb_bwd_apply_local (coalesce + local update, one launch);
@@ -65,7 +65,9 @@ extern "C" {
                                   dqrm_apply_workspace_bytes, dqrm_exchange.apply_ws,
                                   dqrm_exchange_apply_fwd;
                               11: the flat apply's finalize and the next forward in one launch
-                                  (dqrm_apply_sparse_update_fwd), dqrm_apply_fwd_form */
+                                  (dqrm_apply_sparse_update_fwd), dqrm_apply_fwd_form;
+                              12: dqrm_linear (QuantLinear on the f32-input MFMA): dqrm_linear_wquant,
+                                  dqrm_linear_fwd, dqrm_linear_bwd */
 
 /* status codes */
 #define DQRM_OK            0
@@ -562,6 +564,56 @@ int dqrm_dense_grad_decode(const dqrm_dense_set* set, const void* wire, int wire
 /* weight_update_parallel_comm, MLP branch (:641-642 / :659-660):
  *   param += (-lr * grad) * s[c]     (s == NULL: param += -lr * grad, :644-645). */
 int dqrm_dense_update(const dqrm_dense_set* set, const float* s, float lr, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * QuantLinear: the fake-quantized MLP layer (quantization_supp/
+ * quant_modules_not_quantize_grad.py:20-211), csrc/dqrm_linear.hip.
+ * Every `*`, `/` and `+` below is one separately rounded f32 operation, and every sum is the
+ * chain  acc = 0; acc = fmaf(a_k, b_k, acc)  in ascending k (one rounding per product), which
+ * is what v_mfma_f32_16x16x4_f32 computes: the bits are a function of the operands and the
+ * shapes alone (no atomics, no split reductions, the same for every batch slice a row is in).
+ * weight_integer / bias_integer hold integer values as f32, as the reference keeps them.
+ * scale is [out_features] with per_channel, [1] otherwise. All pointers are device pointers.
+ * ------------------------------------------------------------------------------ */
+typedef struct dqrm_linear {
+    int32_t in_features;      /* K */
+    int32_t out_features;     /* O */
+    int32_t weight_bit;       /* 2..32 (quantized calls only) */
+    int32_t bias_bit;         /* 2..32 (quantized calls only) */
+    int32_t per_channel;      /* one scale per output feature / one for the tensor */
+    int32_t reserved;
+    const float* weight;      /* [O][K] */
+    const float* bias;        /* [O] */
+    float* weight_integer;    /* [O][K] */
+    float* bias_integer;      /* [O] */
+    float* scale;             /* [O] or [1]: fc_scaling_factor */
+} dqrm_linear;
+
+/* The quantization half of QuantLinear.forward (q_m_n_q_g.py:121-154):
+ *   n = 2^(weight_bit-1) - 1, nb = 2^(bias_bit-1) - 1
+ *   scale[o] = clamp(max(|min_k W[o,k]|, |max_k W[o,k]|), 1e-8) / n      (quant_utils.py:196-220;
+ *              per_channel == 0: one scale over the whole tensor)
+ *   weight_integer = clamp(round(1/scale * W + 0), -n-1, n)               (quant_utils.py:75-101,329-346)
+ *   bias_integer   = clamp(round(1/scale[o] * b[o] + 0), -nb-1, nb)       (the WEIGHT's scale, :150-154)
+ * One launch with per_channel, two without. */
+int dqrm_linear_wquant(const dqrm_linear* layer, void* stream);
+
+/* QuantLinear.forward's product (q_m_n_q_g.py:209 / :211), x [B][K] -> y [B][O]:
+ *   acc = chain over k of x[b,k] * weight_integer[o,k]
+ *   quantized:      y[b,o] = (acc + bias_integer[o]) * scale[o]   (F.linear(...) * fc_scaling_factor)
+ *   not quantized:  the operands are weight and bias, y[b,o] = acc + bias[o]  (full_precision_flag)
+ * One launch. */
+int dqrm_linear_fwd(const dqrm_linear* layer, int quantized, const float* x, int64_t B, float* y, void* stream);
+
+/* Backward of the above through the straight-through estimator (quant_utils.py:349-363: the
+ * gradient of weight_integer / bias_integer is divided by the scale), g[b,o] = dy[b,o] * scale[o]:
+ *   dx[b,k] = chain over o of g[b,o] * weight_integer[o,k]          (dx == NULL: skipped)
+ *   dw[o,k] = (chain over b of g[b,o] * x[b,k]) / scale[o]
+ *   db[o]   = (chain over b of g[b,o]) / scale[o]
+ * not quantized: scale = 1, the operand is weight, no division. Two launches (db rides in the dw
+ * kernel), one when dx == NULL. */
+int dqrm_linear_bwd(const dqrm_linear* layer, int quantized, const float* x, const float* dy, int64_t B,
+                    float* dx, float* dw, float* db, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Row-wise PTQ formats of the reference's inference path.
