@@ -3,6 +3,8 @@
 Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM):
   * ``quant_modules_not_quantize_grad.QuantEmbeddingBagTwo``  (INT4 fake-quant EmbeddingBag)
   * ``quant_modules_not_quantize_grad.QuantLinear``            (INT4 fake-quant MLP layer, f32 MFMA)
+  * ``DLRM_Net.interact_features``                               (``DotInteraction``: the dot interaction,
+                                                                plain or 16-bit fake-quantized, fused)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
@@ -17,6 +19,7 @@ from .dense import DenseGradExchange
 from . import quant_modules_not_quantize_grad, sgd_quantized_gradients, sgd_quantized_gradients_parallel_comm
 from .quant_modules_not_quantize_grad import QuantEmbeddingBagCollection, QuantEmbeddingBagTwo
 from .linear import QuantLinear
+from .interaction import DotInteraction, interact_features
 from . import quantized_ops
 
 __all__ = [
@@ -36,6 +39,8 @@ __all__ = [
     "QuantEmbeddingBagTwo",
     "QuantEmbeddingBagCollection",
     "QuantLinear",
+    "DotInteraction",
+    "interact_features",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

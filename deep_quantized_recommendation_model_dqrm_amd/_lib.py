@@ -98,6 +98,10 @@ EXPORTED_SYMBOLS = (
     "dqrm_linear_wquant",
     "dqrm_linear_fwd",
     "dqrm_linear_bwd",
+    "dqrm_interact_out_features",
+    "dqrm_interact_scale",
+    "dqrm_interact_fwd",
+    "dqrm_interact_bwd",
     "dqrm_criteo_unpack",
     "dqrm_rowwise_row_bytes",
     "dqrm_rowwise_prepack",
@@ -201,6 +205,19 @@ class Linear(C.Structure):
     ]
 
 
+class Interact(C.Structure):
+    """Mirror of ``dqrm_interact`` (include/dqrm.h)."""
+
+    _fields_ = [
+        ("num_features", C.c_int32),
+        ("dim", C.c_int32),
+        ("self_interaction", C.c_int32),
+        ("quant_bits", C.c_int32),
+        ("emb_stride_b", C.c_int64),
+        ("emb_stride_f", C.c_int64),
+    ]
+
+
 class Exchange(C.Structure):
     """Mirror of ``dqrm_exchange`` (include/dqrm.h): one rank's exchange buffers."""
 
@@ -254,6 +271,7 @@ def load(path: str | None = None) -> C.CDLL:
     BA = C.POINTER(Batch)
     DS = C.POINTER(DenseSet)
     LN = C.POINTER(Linear)
+    IA = C.POINTER(Interact)
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -340,6 +358,10 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_linear_wquant": (C.c_int, [LN, P]),
         "dqrm_linear_fwd": (C.c_int, [LN, C.c_int, P, C.c_int64, P, P]),
         "dqrm_linear_bwd": (C.c_int, [LN, C.c_int, P, P, C.c_int64, P, P, P, P]),
+        "dqrm_interact_out_features": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+        "dqrm_interact_scale": (C.c_int, [IA, P, P, C.c_int64, P, P]),
+        "dqrm_interact_fwd": (C.c_int, [IA, P, P, C.c_int64, P, P, P]),
+        "dqrm_interact_bwd": (C.c_int, [IA, P, P, P, C.c_int64, P, P, P, P]),
         "dqrm_criteo_unpack": (C.c_int, [P, C.c_int64, C.c_int32, P, P, P, P, P]),
         "dqrm_rowwise_row_bytes": (C.c_size_t, [C.c_int, C.c_int]),
         "dqrm_rowwise_prepack": (C.c_int, [C.c_int, P, C.c_int64, C.c_int, P, P]),
@@ -370,7 +392,13 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_abi_version": (C.c_int, []),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # a library built before the symbol was added within this ABI version
+            raise DQRMError(
+                f"{path} does not export {name}: rebuild it with "
+                "`python -m deep_quantized_recommendation_model_dqrm_amd._build`"
+            ) from None
         fn.restype = res
         fn.argtypes = args
     got = lib.dqrm_abi_version()

@@ -67,7 +67,11 @@ extern "C" {
                               11: the flat apply's finalize and the next forward in one launch
                                   (dqrm_apply_sparse_update_fwd), dqrm_apply_fwd_form;
                               12: dqrm_linear (QuantLinear on the f32-input MFMA): dqrm_linear_wquant,
-                                  dqrm_linear_fwd, dqrm_linear_bwd */
+                                  dqrm_linear_fwd, dqrm_linear_bwd;
+                                  added within 12 (new symbols only, no existing signature or
+                                  struct changed): dqrm_interact (the dot feature interaction):
+                                  dqrm_interact_out_features, dqrm_interact_scale,
+                                  dqrm_interact_fwd, dqrm_interact_bwd */
 
 /* status codes */
 #define DQRM_OK            0
@@ -614,6 +618,64 @@ int dqrm_linear_fwd(const dqrm_linear* layer, int quantized, const float* x, int
  * kernel), one when dx == NULL. */
 int dqrm_linear_bwd(const dqrm_linear* layer, int quantized, const float* x, const float* dy, int64_t B,
                     float* dx, float* dw, float* db, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * DotInteraction: DLRM_Net.interact_features, arch_interaction_op "dot"
+ * (dlrm_s_pytorch_comm_grad.py:701-806), csrc/dqrm_interact.hip.
+ * A sample has F = num_features vectors of dim D: T[b,0,:] = x[b,:] (the bottom MLP's output) and
+ * T[b,f,:] = emb[b*emb_stride_b + (f-1)*emb_stride_f + :] (the embedding outputs, read in place:
+ * a [B][F-1][D] slab has strides ((F-1)*D, D), a [F-1][B][D] slab (D, B*D)). Pairs are ordered as
+ * the reference's li / lj lists: for i in 0..F-1, for j in 0..i-1 (0..i with self_interaction),
+ * index p(i,j) in that order; P = F(F-1)/2 (+ F). The output is r [B][D + P].
+ * Every sum is the chain  acc = 0; acc = fmaf(a, b, acc)  in ascending index, one rounding per
+ * product, no atomics, no split reductions; every other `*`, `/`, `+` is one separately rounded
+ * f32 operation. In plain mode a sample's bits depend on that sample's operands alone.
+ *
+ * plain (quant_bits == 0):
+ *   r[b, 0:D]        = x[b, :]                                   (a bit copy)
+ *   r[b, D + p(i,j)] = chain over k of T[b,i,k] * T[b,j,k]
+ *   backward, g(i,j) = dr[b, D + p(i,j)]:
+ *     c(i,j) = g(i,j) for j < i, g(j,i) for j > i, g(i,i) + g(i,i) for j == i with
+ *              self_interaction (without it the j == i term is absent)
+ *     dT[b,i,k] = chain over j = 0..F-1 of c(i,j) * T[b,j,k]
+ *     dx[b,k] = dr[b,k] + dT[b,0,k];  demb[b,f-1,k] = dT[b,f,k]   (demb contiguous [B][F-1][D])
+ * quantized (quant_bits = 2..16; the reference hard-codes 16), n = 2^(bits-1) - 1:
+ *   s  = clamp(max over the whole batch of |T|, 1e-8) / n        (quant_utils.py:196-220)
+ *   Ti = clamp(round_half_even(1/s * T + 0), -n-1, n)            (quant_utils.py:75-101, :329-346)
+ *   r[b, D + p(i,j)] = (chain over k of Ti[i,k] * Ti[j,k]) * (s * s);  r[b, 0:D] = x[b, :]
+ *   backward: g(i,j) = dr[b, D + p(i,j)] * (s * s), the same c and chain over Ti, then
+ *     dT = chain / s  (the STE, quant_utils.py:349-363),  dx = dr[b, 0:D] + dT[b,0]
+ *
+ * Argument rules (checked before any device call): 2 <= F <= 64; D a multiple of 4 in 4..256;
+ * quant_bits 0 or 2..16; strides non-negative multiples of 4; pointers 16-byte aligned (scale:
+ * 4-byte); B >= 0 (B == 0: DQRM_OK, no launch) and B * F * D / 4 < 2^31 (DQRM_E_CAPACITY);
+ * scale non-NULL exactly when quant_bits != 0. No call allocates, synchronises or reads back:
+ * the step can be captured in a HIP graph.
+ * ------------------------------------------------------------------------------ */
+typedef struct dqrm_interact {
+    int32_t num_features;      /* F = tables + 1 */
+    int32_t dim;               /* D */
+    int32_t self_interaction;  /* arch_interaction_itself */
+    int32_t quant_bits;        /* 0: plain; 2..16: the fake-quantized product */
+    int64_t emb_stride_b;      /* elements between two samples of emb */
+    int64_t emb_stride_f;      /* elements between two features of emb (the inner stride is 1) */
+} dqrm_interact;
+
+/* D + P, or a negative value for arguments outside the rules above. */
+int64_t dqrm_interact_out_features(int32_t num_features, int32_t dim, int32_t self_interaction);
+
+/* Quantized mode only: scale[0] = s on the device. A 4-byte memset and one launch, no host read. */
+int dqrm_interact_scale(const dqrm_interact* cfg, const float* x, const float* emb, int64_t B, float* scale,
+                        void* stream);
+
+/* r [B][D + P]. One launch. scale: the device word dqrm_interact_scale wrote (NULL in plain mode). */
+int dqrm_interact_fwd(const dqrm_interact* cfg, const float* x, const float* emb, int64_t B, const float* scale,
+                      float* r, void* stream);
+
+/* dx [B][D] and demb [B][F-1][D] from dr [B][D + P]; either may be NULL (not computed; both NULL:
+ * no launch). One launch. scale: the one the forward used. */
+int dqrm_interact_bwd(const dqrm_interact* cfg, const float* x, const float* emb, const float* dr, int64_t B,
+                      const float* scale, float* dx, float* demb, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Row-wise PTQ formats of the reference's inference path.
