@@ -56,6 +56,10 @@ DQRM_WIRE_F16 = 1
 DQRM_WIRE_I32 = 2
 DQRM_WIRE_F32 = 3
 
+DQRM_ACT_NONE = 0
+DQRM_ACT_RELU = 1
+DQRM_ACT_SIGMOID = 2
+
 DQRM_ABI_VERSION = 12  # include/dqrm.h
 DQRM_PRESUM_MAX_LOOKUPS = 2048
 
@@ -98,6 +102,8 @@ EXPORTED_SYMBOLS = (
     "dqrm_linear_wquant",
     "dqrm_linear_fwd",
     "dqrm_linear_bwd",
+    "dqrm_linear_fwd_act",
+    "dqrm_linear_bwd_act",
     "dqrm_interact_out_features",
     "dqrm_interact_scale",
     "dqrm_interact_fwd",
@@ -358,6 +364,8 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_linear_wquant": (C.c_int, [LN, P]),
         "dqrm_linear_fwd": (C.c_int, [LN, C.c_int, P, C.c_int64, P, P]),
         "dqrm_linear_bwd": (C.c_int, [LN, C.c_int, P, P, C.c_int64, P, P, P, P]),
+        "dqrm_linear_fwd_act": (C.c_int, [LN, C.c_int, C.c_int, P, C.c_int64, P, P]),
+        "dqrm_linear_bwd_act": (C.c_int, [LN, C.c_int, C.c_int, P, P, P, C.c_int64, P, P, P, P]),
         "dqrm_interact_out_features": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
         "dqrm_interact_scale": (C.c_int, [IA, P, P, C.c_int64, P, P]),
         "dqrm_interact_fwd": (C.c_int, [IA, P, P, C.c_int64, P, P, P]),

@@ -8,8 +8,10 @@
 //   linear_quantize                  quant_utils.py:75-101     round(1/s * x + 0)
 //   SymmetricQuantFunction           quant_utils.py:316-363    clamp forward, grad / s backward (STE)
 //
-// Three entry points: dqrm_linear_wquant (scale + integer weights and bias), dqrm_linear_fwd
-// and dqrm_linear_bwd. All three matrix products go through ONE LDS-tiled kernel template on
+// Entry points: dqrm_linear_wquant (scale + integer weights and bias), dqrm_linear_fwd_act and
+// dqrm_linear_bwd_act (the layer with the MLP's ReLU / Sigmoid fused in), and dqrm_linear_fwd /
+// _bwd, which are those two without an activation. All three matrix products go through ONE
+// LDS-tiled kernel template on
 // v_mfma_f32_16x16x4_f32, which is bit for bit an f32 fmaf chain in ascending k with one
 // rounding per product: every output element is
 //     acc = 0;  for k = 0..K-1: acc = fmaf(a[k], b[k], acc)
@@ -27,7 +29,8 @@
 // global loads in flight during the MFMAs.
 //
 // Compiled with -ffp-contract=off: `g = dy * s`, `(acc + bi) * s` and `acc / s` are separately
-// rounded operations, as the reference's autograd graph performs them.
+// rounded operations, as the reference's autograd graph performs them; so are the activation's
+// `1 / (1 + expf(-z))` and its derivative `(dy * (1 - y)) * y`.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -145,6 +148,10 @@ __global__ void __launch_bounds__(QWG) k_wquant_tensor(QuantArgs a) {
 //             and, in the workgroups of the first tile column, db[m] = (chain over k of A(m,k)) / s[m]
 // s == nullptr: s = 1 (full precision: multiplying or dividing by 1 is exact). s_stride = 0:
 // one scale for the whole tensor.
+// ACT (DQRM_ACT_*), the activation that follows the layer in create_mlp: FWD stores act(C); DX
+// and DW read, beside each dy element, the forward's output y at the same address, and dy above
+// stands for d = dy * act'(y) (RELU: y <= 0 ? 0 : dy; SIGMOID: (dy * (1 - y)) * y), formed before
+// the scale is applied. db sums the staged A tile and so follows.
 enum { FWD = 0, DX = 1, DW = 2 };
 
 struct GemmArgs {
@@ -156,16 +163,20 @@ struct GemmArgs {
     int s_stride;
     const float* bias;  // FWD
     float* db;          // DW
+    const float* Y;     // DX / DW with an activation: the forward's output, laid out as A
 };
 
 // Stage a BK x BMN operand tile into LDS as dst[k][r] (zero outside the matrix).
 // KCONTIG: element (r, k) at src[r * ld + k], lanes run along k; else at src[k * ld + r], lanes
 // run along r. SC: 1 = times s[k], 2 = times s[r] (the STE's g = dy * s, formed on load).
-template <int BMN, int BK, int LDS_LD, bool KCONTIG, int SC>
+// ACT != NONE: a second register stream yv[] holds the forward's output at v[]'s addresses and
+// store() turns v into v * act'(yv) before the scale.
+template <int BMN, int BK, int LDS_LD, bool KCONTIG, int SC, int ACT>
 struct Stage {
     static constexpr int PER = BK * BMN / LWG;
     float v[PER];
     float sv[SC != 0 ? PER : 1];
+    float yv[ACT != DQRM_ACT_NONE ? PER : 1];
     uint32_t ok;  // bit i: element i lies inside the matrix
 
     __device__ __forceinline__ static void pos(int e, int& kk, int& r) {
@@ -179,10 +190,12 @@ struct Stage {
     }
 
     // Issues the stage's loads and nothing that waits for them: every element is loaded
-    // unconditionally (from element (0, 0) when it lies outside the matrix) and the scale is
-    // applied in store(), so the loads stay in flight during the MFMAs between the two calls.
+    // unconditionally (from element (0, 0) when it lies outside the matrix) and the activation's
+    // derivative and the scale are applied in store(), so the loads stay in flight during the
+    // MFMAs between the two calls.
     __device__ __forceinline__ void load(const float* __restrict__ src, int64_t ld, int r0, int k0, int R, int K,
-                                         const float* __restrict__ s, int s_stride) {
+                                         const float* __restrict__ s, int s_stride,
+                                         const float* __restrict__ ysrc) {
         ok = 0;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
@@ -191,7 +204,9 @@ struct Stage {
             const bool in = r0 + r < R && k0 + kk < K;
             const int gr = in ? r0 + r : 0, gk = in ? k0 + kk : 0;
             ok |= (uint32_t)in << i;
-            v[i] = KCONTIG ? src[(int64_t)gr * ld + gk] : src[(int64_t)gk * ld + gr];
+            const int64_t at = KCONTIG ? (int64_t)gr * ld + gk : (int64_t)gk * ld + gr;
+            v[i] = src[at];
+            if (ACT != DQRM_ACT_NONE) yv[i] = ysrc[at];
             if (SC != 0) sv[i] = s != nullptr ? s[(int64_t)(SC == 1 ? gk : gr) * s_stride] : 1.0f;
         }
     }
@@ -202,13 +217,15 @@ struct Stage {
             int kk, r;
             pos((int)threadIdx.x + i * LWG, kk, r);
             float x = v[i];
+            if (ACT == DQRM_ACT_RELU) x = yv[i] <= 0.0f ? 0.0f : x;
+            if (ACT == DQRM_ACT_SIGMOID) x = (x * (1.0f - yv[i])) * yv[i];
             if (SC != 0) x = x * sv[i];
             dst[kk][r] = (ok >> i) & 1u ? x : 0.0f;
         }
     }
 };
 
-template <int WT, int MODE>
+template <int WT, int MODE, int ACT>
 __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     constexpr int BT = 32 * WT;      // workgroup tile edge
     constexpr int BK = 64 / WT;      // k per LDS stage (16 or 8 MFMA k-steps; 8 floats per thread and operand)
@@ -218,6 +235,7 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     constexpr bool A_KC = MODE != DW;
     constexpr bool B_KC = MODE == FWD;
     constexpr int A_SC = MODE == DX ? 1 : (MODE == DW ? 2 : 0);
+    constexpr int A_ACT = MODE == FWD ? DQRM_ACT_NONE : ACT;  // FWD applies it in the epilogue
     __shared__ float As[2][BK][LD];
     __shared__ float Bs[2][BK][LD];
 
@@ -236,19 +254,19 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     const bool do_db = MODE == DW && blockIdx.x == 0 && tid < BT;
     float dbacc = 0.0f;
 
-    Stage<BT, BK, LD, A_KC, A_SC> sa;
-    Stage<BT, BK, LD, B_KC, 0> sb;
+    Stage<BT, BK, LD, A_KC, A_SC, A_ACT> sa;
+    Stage<BT, BK, LD, B_KC, 0, DQRM_ACT_NONE> sb;
     const int T = (g.K + BK - 1) / BK;
-    sa.load(g.A, lda, m0, 0, g.M, g.K, g.s, g.s_stride);
-    sb.load(g.B, ldb, n0, 0, g.N, g.K, nullptr, 0);
+    sa.load(g.A, lda, m0, 0, g.M, g.K, g.s, g.s_stride, g.Y);
+    sb.load(g.B, ldb, n0, 0, g.N, g.K, nullptr, 0, nullptr);
     sa.store(As[0]);
     sb.store(Bs[0]);
     __syncthreads();
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
         if (t + 1 < T) {  // in flight during the MFMAs below
-            sa.load(g.A, lda, m0, (t + 1) * BK, g.M, g.K, g.s, g.s_stride);
-            sb.load(g.B, ldb, n0, (t + 1) * BK, g.N, g.K, nullptr, 0);
+            sa.load(g.A, lda, m0, (t + 1) * BK, g.M, g.K, g.s, g.s_stride, g.Y);
+            sb.load(g.B, ldb, n0, (t + 1) * BK, g.N, g.K, nullptr, 0, nullptr);
         }
 #pragma unroll
         for (int ks = 0; ks < BK / 4; ++ks) {
@@ -291,7 +309,11 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
                 const int m = m0 + wm + i * 16 + lk * 4 + r;
                 if (m >= g.M) continue;
                 float c = acc[i][j][r];
-                if (MODE == FWD) c = (c + bn) * sn;
+                if (MODE == FWD) {
+                    c = (c + bn) * sn;
+                    if (ACT == DQRM_ACT_RELU) c = c <= 0.0f ? 0.0f : c;  // keeps a NaN, -0 becomes +0
+                    if (ACT == DQRM_ACT_SIGMOID) c = 1.0f / (1.0f + expf(-c));
+                }
                 if (MODE == DW && g.s != nullptr) c = c / g.s[(int64_t)m * g.s_stride];
                 g.C[(int64_t)m * g.N + n] = c;
             }
@@ -306,18 +328,33 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
 // a 256-CU part, 64 x 64 beyond. The bits do not depend on it.
 constexpr int64_t kSmallTileMax = 1024;
 
-template <int MODE>
-int launch_gemm(const GemmArgs& g, hipStream_t st, const char* what) {
+template <int MODE, int ACT>
+int launch_gemm_act(const GemmArgs& g, hipStream_t st, const char* what) {
     const int64_t bm = (g.M + 31) / 32, bn = (g.N + 31) / 32;
     if (bm * bn < kSmallTileMax) {
         if (bm > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
-        hipLaunchKernelGGL((k_linear_gemm<1, MODE>), dim3((unsigned)bn, (unsigned)bm), dim3(LWG), 0, st, g);
+        hipLaunchKernelGGL((k_linear_gemm<1, MODE, ACT>), dim3((unsigned)bn, (unsigned)bm), dim3(LWG), 0, st, g);
     } else {
         const int64_t bm2 = (g.M + 63) / 64, bn2 = (g.N + 63) / 64;
         if (bm2 > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
-        hipLaunchKernelGGL((k_linear_gemm<2, MODE>), dim3((unsigned)bn2, (unsigned)bm2), dim3(LWG), 0, st, g);
+        hipLaunchKernelGGL((k_linear_gemm<2, MODE, ACT>), dim3((unsigned)bn2, (unsigned)bm2), dim3(LWG), 0, st, g);
     }
     LHIP_TRY(hipGetLastError());
+    return DQRM_OK;
+}
+
+template <int MODE>
+int launch_gemm(const GemmArgs& g, int act, hipStream_t st, const char* what) {
+    switch (act) {
+        case DQRM_ACT_RELU: return launch_gemm_act<MODE, DQRM_ACT_RELU>(g, st, what);
+        case DQRM_ACT_SIGMOID: return launch_gemm_act<MODE, DQRM_ACT_SIGMOID>(g, st, what);
+        default: return launch_gemm_act<MODE, DQRM_ACT_NONE>(g, st, what);
+    }
+}
+
+int check_act(int act, const char* what) {
+    if (act < DQRM_ACT_NONE || act > DQRM_ACT_SIGMOID)
+        return linear_error(DQRM_E_INVALID, "%s: act must be DQRM_ACT_NONE, _RELU or _SIGMOID (got %d)", what, act);
     return DQRM_OK;
 }
 
@@ -360,12 +397,19 @@ int dqrm_linear_wquant(const dqrm_linear* l, void* stream) {
     return DQRM_OK;
 }
 
-int dqrm_linear_fwd(const dqrm_linear* l, int quantized, const float* x, int64_t B, float* y, void* stream) {
-    int rc = check_linear(l, quantized, "dqrm_linear_fwd");
+}  // extern "C"
+
+namespace {
+
+// dqrm_linear_fwd / _fwd_act and dqrm_linear_bwd / _bwd_act (`what` names the export in errors)
+int linear_fwd(const dqrm_linear* l, int quantized, int act, const float* x, int64_t B, float* y, void* stream,
+               const char* what) {
+    int rc = check_linear(l, quantized, what);
     if (rc) return rc;
-    if (B < 0 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "dqrm_linear_fwd: bad batch size");
+    if ((rc = check_act(act, what))) return rc;
+    if (B < 0 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
     if (B == 0) return DQRM_OK;
-    if (!x || !y) return linear_error(DQRM_E_INVALID, "dqrm_linear_fwd: null x / y");
+    if (!x || !y) return linear_error(DQRM_E_INVALID, "%s: null x / y", what);
     GemmArgs g{};
     g.M = (int)B;
     g.N = l->out_features;
@@ -376,17 +420,21 @@ int dqrm_linear_fwd(const dqrm_linear* l, int quantized, const float* x, int64_t
     g.s = quantized ? l->scale : nullptr;
     g.s_stride = l->per_channel ? 1 : 0;
     g.bias = quantized ? l->bias_integer : l->bias;
-    return launch_gemm<FWD>(g, (hipStream_t)stream, "dqrm_linear_fwd");
+    return launch_gemm<FWD>(g, act, (hipStream_t)stream, what);
 }
 
-int dqrm_linear_bwd(const dqrm_linear* l, int quantized, const float* x, const float* dy, int64_t B, float* dx,
-                    float* dw, float* db, void* stream) {
-    int rc = check_linear(l, quantized, "dqrm_linear_bwd");
+int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, const float* y, const float* dy,
+               int64_t B, float* dx, float* dw, float* db, void* stream, const char* what) {
+    int rc = check_linear(l, quantized, what);
     if (rc) return rc;
-    if (B < 1 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "dqrm_linear_bwd: bad batch size");
-    if (!x || !dy || !dw || !db) return linear_error(DQRM_E_INVALID, "dqrm_linear_bwd: null x / dy / dw / db");
+    if ((rc = check_act(act, what))) return rc;
+    if (B < 1 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!x || !dy || !dw || !db) return linear_error(DQRM_E_INVALID, "%s: null x / dy / dw / db", what);
+    if (act != DQRM_ACT_NONE && !y)
+        return linear_error(DQRM_E_INVALID, "%s: an activation's backward needs the forward's output (null y)", what);
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g{};
+    g.Y = act != DQRM_ACT_NONE ? y : nullptr;
     g.s = quantized ? l->scale : nullptr;
     g.s_stride = l->per_channel ? 1 : 0;
     if (dx) {
@@ -396,7 +444,7 @@ int dqrm_linear_bwd(const dqrm_linear* l, int quantized, const float* x, const f
         g.A = dy;
         g.B = quantized ? l->weight_integer : l->weight;
         g.C = dx;
-        if ((rc = launch_gemm<DX>(g, st, "dqrm_linear_bwd"))) return rc;
+        if ((rc = launch_gemm<DX>(g, act, st, what))) return rc;
     }
     g.M = l->out_features;
     g.N = l->in_features;
@@ -405,7 +453,30 @@ int dqrm_linear_bwd(const dqrm_linear* l, int quantized, const float* x, const f
     g.B = x;
     g.C = dw;
     g.db = db;
-    return launch_gemm<DW>(g, st, "dqrm_linear_bwd");
+    return launch_gemm<DW>(g, act, st, what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dqrm_linear_fwd(const dqrm_linear* l, int quantized, const float* x, int64_t B, float* y, void* stream) {
+    return linear_fwd(l, quantized, DQRM_ACT_NONE, x, B, y, stream, "dqrm_linear_fwd");
+}
+
+int dqrm_linear_bwd(const dqrm_linear* l, int quantized, const float* x, const float* dy, int64_t B, float* dx,
+                    float* dw, float* db, void* stream) {
+    return linear_bwd(l, quantized, DQRM_ACT_NONE, x, nullptr, dy, B, dx, dw, db, stream, "dqrm_linear_bwd");
+}
+
+int dqrm_linear_fwd_act(const dqrm_linear* l, int quantized, int act, const float* x, int64_t B, float* y,
+                        void* stream) {
+    return linear_fwd(l, quantized, act, x, B, y, stream, "dqrm_linear_fwd_act");
+}
+
+int dqrm_linear_bwd_act(const dqrm_linear* l, int quantized, int act, const float* x, const float* y,
+                        const float* dy, int64_t B, float* dx, float* dw, float* db, void* stream) {
+    return linear_bwd(l, quantized, act, x, y, dy, B, dx, dw, db, stream, "dqrm_linear_bwd_act");
 }
 
 }  // extern "C"

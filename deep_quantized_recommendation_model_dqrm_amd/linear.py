@@ -20,6 +20,11 @@ buffer names and state-dict keys of ``set_param`` (:70-97), ``__repr__`` (:64-68
 Every sum is an f32 fmaf chain in ascending index (include/dqrm.h), so a row's output does not
 depend on the batch it is part of and every data-parallel replica computes the same bits.
 
+``QuantLinear.activation`` (None, "relu" or "sigmoid"; mlp.fuse_activations sets it) fuses the
+activation that follows the layer in ``create_mlp`` into the same launches: dqrm_linear_fwd_act
+applies it in the forward's epilogue and dqrm_linear_bwd_act multiplies ``dy`` by its derivative,
+read from the saved output, where the STE's scale is applied.
+
 Not built: ``QuantAct`` / activation quantization (``quantize_activation=True``, a
 ``prev_act_scaling_factor``) and asymmetric weights (the reference raises there too).
 """
@@ -35,6 +40,9 @@ from . import _lib as L
 from .tables import _stream_handle
 
 
+_ACTS = {None: L.DQRM_ACT_NONE, "relu": L.DQRM_ACT_RELU, "sigmoid": L.DQRM_ACT_SIGMOID}
+
+
 def _check_input(x: torch.Tensor, layer: "QuantLinear") -> None:
     w = layer.weight
     if x.device.type != "cuda" or w.device.type != "cuda":
@@ -48,43 +56,62 @@ def _check_input(x: torch.Tensor, layer: "QuantLinear") -> None:
 
 
 class _LinearFn(torch.autograd.Function):
-    """Autograd bridge over dqrm_linear_wquant / _fwd / _bwd. The backward reads the integers and
-    scale the layer's latest forward wrote (the same ones unless the weights changed in between)."""
+    """Autograd bridge over dqrm_linear_wquant / _fwd / _bwd (act == DQRM_ACT_NONE) or
+    _fwd_act / _bwd_act. The backward reads the integers and scale the layer's latest forward
+    wrote (the same ones unless the weights changed in between); with an activation it also reads
+    the output, saved with x so that autograd's version check catches an in-place write to it."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, owner, quantized):
+    def forward(ctx, x, weight, bias, owner, quantized, act=L.DQRM_ACT_NONE):
         lib, c, st = owner._lib, owner._c_struct(), _stream_handle()
         if quantized:
             L.check(lib.dqrm_linear_wquant(C.byref(c), st), "dqrm_linear_wquant")
         y = torch.empty((x.shape[0], owner.out_features), dtype=torch.float32, device=x.device)
-        L.check(lib.dqrm_linear_fwd(C.byref(c), int(quantized), x.data_ptr(), x.shape[0], y.data_ptr(), st),
-                "dqrm_linear_fwd")
-        ctx.save_for_backward(x)
+        if act == L.DQRM_ACT_NONE:
+            L.check(lib.dqrm_linear_fwd(C.byref(c), int(quantized), x.data_ptr(), x.shape[0], y.data_ptr(), st),
+                    "dqrm_linear_fwd")
+            ctx.save_for_backward(x)
+        else:
+            L.check(lib.dqrm_linear_fwd_act(C.byref(c), int(quantized), act, x.data_ptr(), x.shape[0],
+                                            y.data_ptr(), st), "dqrm_linear_fwd_act")
+            ctx.save_for_backward(x, y)
         ctx.owner = owner
         ctx.quantized = quantized
+        ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, *ys = ctx.saved_tensors
         owner = ctx.owner
         dy = dy.contiguous()
         B = x.shape[0]
         dw = torch.empty_like(owner.weight)
         db = torch.empty_like(owner.bias)
         if B == 0:
-            return (torch.empty_like(x) if ctx.needs_input_grad[0] else None), dw.zero_(), db.zero_(), None, None
+            return ((torch.empty_like(x) if ctx.needs_input_grad[0] else None), dw.zero_(), db.zero_(), None, None,
+                    None)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        L.check(owner._lib.dqrm_linear_bwd(C.byref(owner._c_struct()), int(ctx.quantized), x.data_ptr(),
-                                           dy.data_ptr(), B, None if dx is None else dx.data_ptr(),
-                                           dw.data_ptr(), db.data_ptr(), _stream_handle()),
-                "dqrm_linear_bwd")
-        return dx, dw, db, None, None
+        if ctx.act == L.DQRM_ACT_NONE:
+            L.check(owner._lib.dqrm_linear_bwd(C.byref(owner._c_struct()), int(ctx.quantized), x.data_ptr(),
+                                               dy.data_ptr(), B, None if dx is None else dx.data_ptr(),
+                                               dw.data_ptr(), db.data_ptr(), _stream_handle()),
+                    "dqrm_linear_bwd")
+        else:
+            L.check(owner._lib.dqrm_linear_bwd_act(C.byref(owner._c_struct()), int(ctx.quantized), ctx.act,
+                                                   x.data_ptr(), ys[0].data_ptr(), dy.data_ptr(), B,
+                                                   None if dx is None else dx.data_ptr(), dw.data_ptr(),
+                                                   db.data_ptr(), _stream_handle()),
+                    "dqrm_linear_bwd_act")
+        return dx, dw, db, None, None, None
 
 
 class QuantLinear(nn.Module):
     """quant_modules_not_quantize_grad.py:20-211 on libdqrm: constructor arguments, defaults,
-    buffers and forward signature of the reference."""
+    buffers and forward signature of the reference. ``activation`` (not a constructor argument:
+    None, "relu" or "sigmoid") is the activation fused into the layer's kernels."""
+
+    activation = None  # class default: a layer pickled before the attribute existed reads None
 
     def __init__(self, weight_bit=4, bias_bit=None, full_precision_flag=False, quant_mode="symmetric",
                  per_channel=False, fix_flag=False, weight_percentile=0, quantize_activation=False):
@@ -182,13 +209,17 @@ class QuantLinear(nn.Module):
                 raise TypeError("QuantLinear quantizes its bias: bias_bit must be an int")
         if "weight" not in self._parameters:
             raise RuntimeError("QuantLinear.set_param(linear) has not been called")
+        activation = getattr(self, "activation", None)
+        if not (activation is None or isinstance(activation, str)) or activation not in _ACTS:
+            raise ValueError(f"QuantLinear.activation must be None, 'relu' or 'sigmoid' (got {activation!r})")
+        act = _ACTS[activation]
         _check_input(x, self)
         if quantized:
             self._scale_buffer()
         if x.device.index != torch.cuda.current_device():
             with torch.cuda.device(x.device):
-                return _LinearFn.apply(x, self.weight, self.bias, self, quantized), None
-        return _LinearFn.apply(x, self.weight, self.bias, self, quantized), None
+                return _LinearFn.apply(x, self.weight, self.bias, self, quantized, act), None
+        return _LinearFn.apply(x, self.weight, self.bias, self, quantized, act), None
 
 
 __all__ = ["QuantLinear"]

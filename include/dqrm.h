@@ -71,7 +71,9 @@ extern "C" {
                                   added within 12 (new symbols only, no existing signature or
                                   struct changed): dqrm_interact (the dot feature interaction):
                                   dqrm_interact_out_features, dqrm_interact_scale,
-                                  dqrm_interact_fwd, dqrm_interact_bwd */
+                                  dqrm_interact_fwd, dqrm_interact_bwd;
+                                  likewise within 12: the MLP's activation fused into the layer,
+                                  DQRM_ACT_*, dqrm_linear_fwd_act, dqrm_linear_bwd_act */
 
 /* status codes */
 #define DQRM_OK            0
@@ -618,6 +620,33 @@ int dqrm_linear_fwd(const dqrm_linear* layer, int quantized, const float* x, int
  * kernel), one when dx == NULL. */
 int dqrm_linear_bwd(const dqrm_linear* layer, int quantized, const float* x, const float* dy, int64_t B,
                     float* dx, float* dw, float* db, void* stream);
+
+/* The activation create_mlp puts after every layer (dlrm_s_pytorch_comm_grad.py:279-343: nn.ReLU,
+ * nn.Sigmoid after the last), fused into the layer's kernels. Let z[b,o] be exactly what
+ * dqrm_linear_fwd produces (chain, bias and scale included); every operation named is one
+ * separately rounded f32 operation:
+ *
+ *   act               forward y[b,o]                   backward d[b,o]
+ *   DQRM_ACT_NONE     z                                dy
+ *   DQRM_ACT_RELU     z <= 0 ? 0 : z                   y <= 0 ? 0 : dy
+ *   DQRM_ACT_SIGMOID  1.0f / (1.0f + expf(-z))         (dy * (1.0f - y)) * y
+ *
+ * RELU keeps a NaN and turns -0 into +0; its backward is torch's threshold_backward on the
+ * result. SIGMOID's backward is torch's sigmoid_backward in its order of operations.
+ * d replaces dy in dqrm_linear_bwd's formulas: g[b,o] = d[b,o] * scale[o], and dx, dw and db are
+ * the unchanged chains over g (dx == NULL: skipped). y is the forward's output [B][O], read with
+ * dy's addressing: required when act != DQRM_ACT_NONE, ignored (may be NULL) when it is.
+ * DQRM_E_INVALID before any device work: act outside 0..2, act != NONE with y == NULL in the
+ * backward, and everything dqrm_linear_fwd / _bwd reject. With DQRM_ACT_NONE the calls are
+ * dqrm_linear_fwd / _bwd bit for bit. The launch counts do not change: forward one, backward
+ * two, one when dx == NULL. */
+enum { DQRM_ACT_NONE = 0, DQRM_ACT_RELU = 1, DQRM_ACT_SIGMOID = 2 };
+
+int dqrm_linear_fwd_act(const dqrm_linear* layer, int quantized, int act,
+                        const float* x, int64_t B, float* y, void* stream);
+int dqrm_linear_bwd_act(const dqrm_linear* layer, int quantized, int act,
+                        const float* x, const float* y, const float* dy, int64_t B,
+                        float* dx, float* dw, float* db, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * DotInteraction: DLRM_Net.interact_features, arch_interaction_op "dot"
