@@ -3,6 +3,8 @@
 Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM):
   * ``quant_modules_not_quantize_grad.QuantEmbeddingBagTwo``  (INT4 fake-quant EmbeddingBag)
   * ``quant_modules_not_quantize_grad.QuantLinear``            (INT4 fake-quant MLP layer, f32 MFMA)
+  * ``quant_modules_not_quantize_grad.QuantAct``               (activation quantization with a running
+                                                                range kept on the device)
   * ``DLRM_Net.create_mlp`` / ``apply_mlp``                      (``mlp``: the MLP stacks, ReLU / Sigmoid
                                                                 fused into the layers' kernels)
   * ``DLRM_Net.interact_features``                               (``DotInteraction``: the dot interaction,
@@ -21,6 +23,7 @@ from .dense import DenseGradExchange
 from . import quant_modules_not_quantize_grad, sgd_quantized_gradients, sgd_quantized_gradients_parallel_comm
 from .quant_modules_not_quantize_grad import QuantEmbeddingBagCollection, QuantEmbeddingBagTwo
 from .linear import QuantLinear
+from .act import QuantAct
 from .mlp import FusedActivation, apply_mlp, create_mlp, fuse_activations, unfuse_activations
 from .interaction import DotInteraction, interact_features
 from . import quantized_ops
@@ -42,6 +45,7 @@ __all__ = [
     "QuantEmbeddingBagTwo",
     "QuantEmbeddingBagCollection",
     "QuantLinear",
+    "QuantAct",
     "create_mlp",
     "apply_mlp",
     "fuse_activations",

@@ -104,6 +104,12 @@ EXPORTED_SYMBOLS = (
     "dqrm_linear_bwd",
     "dqrm_linear_fwd_act",
     "dqrm_linear_bwd_act",
+    "dqrm_linear_wquant_qact",
+    "dqrm_linear_fwd_qact",
+    "dqrm_linear_bwd_qact",
+    "dqrm_act_quant_workspace_bytes",
+    "dqrm_act_quant_fwd",
+    "dqrm_act_quant_bwd",
     "dqrm_interact_out_features",
     "dqrm_interact_scale",
     "dqrm_interact_fwd",
@@ -211,6 +217,20 @@ class Linear(C.Structure):
     ]
 
 
+class ActQuant(C.Structure):
+    """Mirror of ``dqrm_act_quant`` (include/dqrm.h)."""
+
+    _fields_ = [
+        ("activation_bit", C.c_int32),
+        ("running_stat", C.c_int32),
+        ("momentum", C.c_float),
+        ("one_minus_momentum", C.c_float),
+        ("x_min", C.c_void_p),
+        ("x_max", C.c_void_p),
+        ("scale", C.c_void_p),
+    ]
+
+
 class Interact(C.Structure):
     """Mirror of ``dqrm_interact`` (include/dqrm.h)."""
 
@@ -278,6 +298,7 @@ def load(path: str | None = None) -> C.CDLL:
     DS = C.POINTER(DenseSet)
     LN = C.POINTER(Linear)
     IA = C.POINTER(Interact)
+    AQ = C.POINTER(ActQuant)
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -366,6 +387,12 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_linear_bwd": (C.c_int, [LN, C.c_int, P, P, C.c_int64, P, P, P, P]),
         "dqrm_linear_fwd_act": (C.c_int, [LN, C.c_int, C.c_int, P, C.c_int64, P, P]),
         "dqrm_linear_bwd_act": (C.c_int, [LN, C.c_int, C.c_int, P, P, P, C.c_int64, P, P, P, P]),
+        "dqrm_linear_wquant_qact": (C.c_int, [LN, P, P, P]),
+        "dqrm_linear_fwd_qact": (C.c_int, [LN, C.c_int, P, P, P, C.c_int64, P, P]),
+        "dqrm_linear_bwd_qact": (C.c_int, [LN, C.c_int, P, P, P, P, P, C.c_int64, P, P, P, P]),
+        "dqrm_act_quant_workspace_bytes": (C.c_int64, [C.c_int64]),
+        "dqrm_act_quant_fwd": (C.c_int, [AQ, P, C.c_int64, P, P, P]),
+        "dqrm_act_quant_bwd": (C.c_int, [P, P, C.c_int64, P, P]),
         "dqrm_interact_out_features": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
         "dqrm_interact_scale": (C.c_int, [IA, P, P, C.c_int64, P, P]),
         "dqrm_interact_fwd": (C.c_int, [IA, P, P, C.c_int64, P, P, P]),

@@ -10,7 +10,9 @@
 //
 // Entry points: dqrm_linear_wquant (scale + integer weights and bias), dqrm_linear_fwd_act and
 // dqrm_linear_bwd_act (the layer with the MLP's ReLU / Sigmoid fused in), and dqrm_linear_fwd /
-// _bwd, which are those two without an activation. All three matrix products go through ONE
+// _bwd, which are those two without an activation; dqrm_linear_wquant_qact / _fwd_qact /
+// _bwd_qact are the integer-activation branch (quantize_activation with a previous activation
+// scale, q_m_n_q_g.py:150-161, :193-196) on the same kernels. All three matrix products go through ONE
 // LDS-tiled kernel template on
 // v_mfma_f32_16x16x4_f32, which is bit for bit an f32 fmaf chain in ascending k with one
 // rounding per product: every output element is
@@ -91,10 +93,26 @@ struct QuantArgs {
     float n;              // 2^(weight_bit-1) - 1
     float wlo, whi;       // weight clamp
     float blo, bhi;       // bias clamp
+    const float* prev;    // QA: the previous activation scale p, one float
+    float* cos;           // QA: out_scale[o] = scale[o] * p, [out] or [1]
 };
+
+// QA (the integer-activation branch, q_m_n_q_g.py:150-154): the bias is quantized with
+// cos = s * p in place of s, and cos is stored at cos[cos_at] (cos_at < 0: by another row).
+template <bool QA>
+__device__ __forceinline__ void quant_bias(const QuantArgs& a, int o, float s, float rcp, int cos_at) {
+    if (QA) {
+        const float c = s * a.prev[0];
+        if (cos_at >= 0) a.cos[cos_at] = c;
+        a.bi[o] = quant1(a.b[o], 1.0f / c, a.blo, a.bhi);
+    } else {
+        a.bi[o] = quant1(a.b[o], rcp, a.blo, a.bhi);
+    }
+}
 
 // per_channel: one wave per weight row: s[o] = clamp(max(|min_k W|, |max_k W|), 1e-8) / n
 // (== max_k |W| for finite W), the row's integers, and the row's bias integer.
+template <bool QA>
 __global__ void __launch_bounds__(QWG) k_wquant_rows(QuantArgs a) {
     const int o = blockIdx.x * QRPW + threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     if (o >= a.out) return;
@@ -108,7 +126,7 @@ __global__ void __launch_bounds__(QWG) k_wquant_rows(QuantArgs a) {
     for (int k = lane; k < a.in; k += WAVE) wi[k] = quant1(w[k], rcp, a.wlo, a.whi);
     if (lane == 0) {
         a.scale[o] = s;
-        a.bi[o] = quant1(a.b[o], rcp, a.blo, a.bhi);
+        quant_bias<QA>(a, o, s, rcp, o);
     }
 }
 
@@ -130,14 +148,16 @@ __global__ void __launch_bounds__(AWG) k_wquant_absmax(QuantArgs a) {
 }
 
 // per tensor, launch 2: the integers of every row and bias with scale[0]
+template <bool QA>
 __global__ void __launch_bounds__(QWG) k_wquant_tensor(QuantArgs a) {
     const int o = blockIdx.x * QRPW + threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     if (o >= a.out) return;
     const float* __restrict__ w = a.W + (int64_t)o * a.in;
     float* __restrict__ wi = a.wi + (int64_t)o * a.in;
-    const float rcp = 1.0f / a.scale[0];
+    const float s = a.scale[0];
+    const float rcp = 1.0f / s;
     for (int k = lane; k < a.in; k += WAVE) wi[k] = quant1(w[k], rcp, a.wlo, a.whi);
-    if (lane == 0) a.bi[o] = quant1(a.b[o], rcp, a.blo, a.bhi);
+    if (lane == 0) quant_bias<QA>(a, o, s, rcp, o == 0 ? 0 : -1);
 }
 
 // ------------------------------------------------------------------------------ the GEMM
@@ -152,6 +172,13 @@ __global__ void __launch_bounds__(QWG) k_wquant_tensor(QuantArgs a) {
 // and DW read, beside each dy element, the forward's output y at the same address, and dy above
 // stands for d = dy * act'(y) (RELU: y <= 0 ? 0 : dy; SIGMOID: (dy * (1 - y)) * y), formed before
 // the scale is applied. db sums the staged A tile and so follows.
+// QA (the integer-activation branch, q_m_n_q_g.py:158-161, :193-196), p = prev[0], s = cos
+// (out_scale), ws = the weight's scale:
+//   FWD: A(m,k) = x[m][k] / p             C = rintf(acc + bias[n]) * cos[n]
+//   DX:  A(m,k) = dy[m][k] * cos[k]       C = acc / p
+//   DW:  A(m,k) = dy[k][m] * cos[m]       B(k,n) = x[k][n] / p    C = acc / ws[m]
+//        db[m] = (chain over k of A(m,k)) / cos[m]
+// The division by p is formed on load into LDS, like the STE's scale.
 enum { FWD = 0, DX = 1, DW = 2 };
 
 struct GemmArgs {
@@ -164,18 +191,21 @@ struct GemmArgs {
     const float* bias;  // FWD
     float* db;          // DW
     const float* Y;     // DX / DW with an activation: the forward's output, laid out as A
+    const float* prev;  // QA: p
+    const float* ws;    // QA, DW: the weight's scale (s_stride as s)
 };
 
 // Stage a BK x BMN operand tile into LDS as dst[k][r] (zero outside the matrix).
 // KCONTIG: element (r, k) at src[r * ld + k], lanes run along k; else at src[k * ld + r], lanes
-// run along r. SC: 1 = times s[k], 2 = times s[r] (the STE's g = dy * s, formed on load).
+// run along r. SC: 1 = times s[k], 2 = times s[r] (the STE's g = dy * s, formed on load);
+// 3 = divided by the one p store() is given (the integer activation x / p).
 // ACT != NONE: a second register stream yv[] holds the forward's output at v[]'s addresses and
 // store() turns v into v * act'(yv) before the scale.
 template <int BMN, int BK, int LDS_LD, bool KCONTIG, int SC, int ACT>
 struct Stage {
     static constexpr int PER = BK * BMN / LWG;
     float v[PER];
-    float sv[SC != 0 ? PER : 1];
+    float sv[SC == 1 || SC == 2 ? PER : 1];
     float yv[ACT != DQRM_ACT_NONE ? PER : 1];
     uint32_t ok;  // bit i: element i lies inside the matrix
 
@@ -207,11 +237,11 @@ struct Stage {
             const int64_t at = KCONTIG ? (int64_t)gr * ld + gk : (int64_t)gk * ld + gr;
             v[i] = src[at];
             if (ACT != DQRM_ACT_NONE) yv[i] = ysrc[at];
-            if (SC != 0) sv[i] = s != nullptr ? s[(int64_t)(SC == 1 ? gk : gr) * s_stride] : 1.0f;
+            if (SC == 1 || SC == 2) sv[i] = s != nullptr ? s[(int64_t)(SC == 1 ? gk : gr) * s_stride] : 1.0f;
         }
     }
 
-    __device__ __forceinline__ void store(float (*dst)[LDS_LD]) const {
+    __device__ __forceinline__ void store(float (*dst)[LDS_LD], float p) const {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             int kk, r;
@@ -219,13 +249,14 @@ struct Stage {
             float x = v[i];
             if (ACT == DQRM_ACT_RELU) x = yv[i] <= 0.0f ? 0.0f : x;
             if (ACT == DQRM_ACT_SIGMOID) x = (x * (1.0f - yv[i])) * yv[i];
-            if (SC != 0) x = x * sv[i];
+            if (SC == 1 || SC == 2) x = x * sv[i];
+            if (SC == 3) x = x / p;
             dst[kk][r] = (ok >> i) & 1u ? x : 0.0f;
         }
     }
 };
 
-template <int WT, int MODE, int ACT>
+template <int WT, int MODE, int ACT, bool QA>
 __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     constexpr int BT = 32 * WT;      // workgroup tile edge
     constexpr int BK = 64 / WT;      // k per LDS stage (16 or 8 MFMA k-steps; 8 floats per thread and operand)
@@ -234,7 +265,8 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     constexpr int LD = BT + 17;
     constexpr bool A_KC = MODE != DW;
     constexpr bool B_KC = MODE == FWD;
-    constexpr int A_SC = MODE == DX ? 1 : (MODE == DW ? 2 : 0);
+    constexpr int A_SC = MODE == DX ? 1 : (MODE == DW ? 2 : (QA ? 3 : 0));
+    constexpr int B_SC = QA && MODE == DW ? 3 : 0;
     constexpr int A_ACT = MODE == FWD ? DQRM_ACT_NONE : ACT;  // FWD applies it in the epilogue
     __shared__ float As[2][BK][LD];
     __shared__ float Bs[2][BK][LD];
@@ -255,12 +287,13 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
     float dbacc = 0.0f;
 
     Stage<BT, BK, LD, A_KC, A_SC, A_ACT> sa;
-    Stage<BT, BK, LD, B_KC, 0, DQRM_ACT_NONE> sb;
+    Stage<BT, BK, LD, B_KC, B_SC, DQRM_ACT_NONE> sb;
     const int T = (g.K + BK - 1) / BK;
+    const float p = QA ? g.prev[0] : 1.0f;
     sa.load(g.A, lda, m0, 0, g.M, g.K, g.s, g.s_stride, g.Y);
     sb.load(g.B, ldb, n0, 0, g.N, g.K, nullptr, 0, nullptr);
-    sa.store(As[0]);
-    sb.store(Bs[0]);
+    sa.store(As[0], p);
+    sb.store(Bs[0], p);
     __syncthreads();
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
@@ -286,8 +319,8 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
             for (int kk = 0; kk < BK; ++kk) dbacc = dbacc + As[cur][kk][tid];
         }
         if (t + 1 < T) {
-            sa.store(As[cur ^ 1]);
-            sb.store(Bs[cur ^ 1]);
+            sa.store(As[cur ^ 1], p);
+            sb.store(Bs[cur ^ 1], p);
         }
         __syncthreads();
     }
@@ -310,11 +343,13 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
                 if (m >= g.M) continue;
                 float c = acc[i][j][r];
                 if (MODE == FWD) {
-                    c = (c + bn) * sn;
+                    c = QA ? rintf(c + bn) * sn : (c + bn) * sn;
                     if (ACT == DQRM_ACT_RELU) c = c <= 0.0f ? 0.0f : c;  // keeps a NaN, -0 becomes +0
                     if (ACT == DQRM_ACT_SIGMOID) c = 1.0f / (1.0f + expf(-c));
                 }
-                if (MODE == DW && g.s != nullptr) c = c / g.s[(int64_t)m * g.s_stride];
+                if (MODE == DX && QA) c = c / p;
+                if (MODE == DW && QA) c = c / g.ws[(int64_t)m * g.s_stride];
+                if (MODE == DW && !QA && g.s != nullptr) c = c / g.s[(int64_t)m * g.s_stride];
                 g.C[(int64_t)m * g.N + n] = c;
             }
         }
@@ -328,27 +363,27 @@ __global__ void __launch_bounds__(LWG) k_linear_gemm(GemmArgs g) {
 // a 256-CU part, 64 x 64 beyond. The bits do not depend on it.
 constexpr int64_t kSmallTileMax = 1024;
 
-template <int MODE, int ACT>
+template <int MODE, int ACT, bool QA>
 int launch_gemm_act(const GemmArgs& g, hipStream_t st, const char* what) {
     const int64_t bm = (g.M + 31) / 32, bn = (g.N + 31) / 32;
     if (bm * bn < kSmallTileMax) {
         if (bm > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
-        hipLaunchKernelGGL((k_linear_gemm<1, MODE, ACT>), dim3((unsigned)bn, (unsigned)bm), dim3(LWG), 0, st, g);
+        hipLaunchKernelGGL((k_linear_gemm<1, MODE, ACT, QA>), dim3((unsigned)bn, (unsigned)bm), dim3(LWG), 0, st, g);
     } else {
         const int64_t bm2 = (g.M + 63) / 64, bn2 = (g.N + 63) / 64;
         if (bm2 > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
-        hipLaunchKernelGGL((k_linear_gemm<2, MODE, ACT>), dim3((unsigned)bn2, (unsigned)bm2), dim3(LWG), 0, st, g);
+        hipLaunchKernelGGL((k_linear_gemm<2, MODE, ACT, QA>), dim3((unsigned)bn2, (unsigned)bm2), dim3(LWG), 0, st, g);
     }
     LHIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
-template <int MODE>
+template <int MODE, bool QA = false>
 int launch_gemm(const GemmArgs& g, int act, hipStream_t st, const char* what) {
     switch (act) {
-        case DQRM_ACT_RELU: return launch_gemm_act<MODE, DQRM_ACT_RELU>(g, st, what);
-        case DQRM_ACT_SIGMOID: return launch_gemm_act<MODE, DQRM_ACT_SIGMOID>(g, st, what);
-        default: return launch_gemm_act<MODE, DQRM_ACT_NONE>(g, st, what);
+        case DQRM_ACT_RELU: return launch_gemm_act<MODE, DQRM_ACT_RELU, QA>(g, st, what);
+        case DQRM_ACT_SIGMOID: return launch_gemm_act<MODE, DQRM_ACT_SIGMOID, QA>(g, st, what);
+        default: return launch_gemm_act<MODE, DQRM_ACT_NONE, QA>(g, st, what);
     }
 }
 
@@ -374,39 +409,44 @@ int check_linear(const dqrm_linear* l, int quantized, const char* what) {
     return DQRM_OK;
 }
 
-}  // namespace
+// the integer-activation calls: one-float prev and the [O] / [1] out_scale
+int check_qact(const float* prev, const float* out_scale, const char* what) {
+    if (!prev || !out_scale) return linear_error(DQRM_E_INVALID, "%s: null prev / out_scale", what);
+    return DQRM_OK;
+}
 
-extern "C" {
-
-int dqrm_linear_wquant(const dqrm_linear* l, void* stream) {
-    int rc = check_linear(l, 1, "dqrm_linear_wquant");
+// dqrm_linear_wquant (QA = false: prev and out_scale unused) and dqrm_linear_wquant_qact
+template <bool QA>
+int linear_wquant(const dqrm_linear* l, const float* prev, float* out_scale, void* stream, const char* what) {
+    int rc = check_linear(l, 1, what);
     if (rc) return rc;
+    if (QA && (rc = check_qact(prev, out_scale, what))) return rc;
     const int64_t nw = ((int64_t)1 << (l->weight_bit - 1)) - 1, nb = ((int64_t)1 << (l->bias_bit - 1)) - 1;
     QuantArgs a{l->out_features, l->in_features, l->weight, l->bias, l->weight_integer, l->bias_integer,
-                l->scale,        (float)nw,      (float)(-nw - 1), (float)nw, (float)(-nb - 1), (float)nb};
+                l->scale,        (float)nw,      (float)(-nw - 1), (float)nw, (float)(-nb - 1), (float)nb,
+                prev,            out_scale};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((l->out_features + QRPW - 1) / QRPW));
     if (l->per_channel) {
-        hipLaunchKernelGGL(k_wquant_rows, grid, dim3(QWG), 0, st, a);
+        hipLaunchKernelGGL(k_wquant_rows<QA>, grid, dim3(QWG), 0, st, a);
     } else {
         hipLaunchKernelGGL(k_wquant_absmax, dim3(1), dim3(AWG), 0, st, a);
         LHIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_wquant_tensor, grid, dim3(QWG), 0, st, a);
+        hipLaunchKernelGGL(k_wquant_tensor<QA>, grid, dim3(QWG), 0, st, a);
     }
     LHIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// dqrm_linear_fwd / _fwd_act and dqrm_linear_bwd / _bwd_act (`what` names the export in errors)
-int linear_fwd(const dqrm_linear* l, int quantized, int act, const float* x, int64_t B, float* y, void* stream,
-               const char* what) {
+// dqrm_linear_fwd / _fwd_act / _fwd_qact and dqrm_linear_bwd / _bwd_act / _bwd_qact (`what` names
+// the export in errors). QA: quantized, prev and out_scale given.
+template <bool QA>
+int linear_fwd(const dqrm_linear* l, int quantized, int act, const float* x, const float* prev,
+               const float* out_scale, int64_t B, float* y, void* stream, const char* what) {
     int rc = check_linear(l, quantized, what);
     if (rc) return rc;
     if ((rc = check_act(act, what))) return rc;
+    if (QA && (rc = check_qact(prev, out_scale, what))) return rc;
     if (B < 0 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
     if (B == 0) return DQRM_OK;
     if (!x || !y) return linear_error(DQRM_E_INVALID, "%s: null x / y", what);
@@ -417,17 +457,21 @@ int linear_fwd(const dqrm_linear* l, int quantized, int act, const float* x, int
     g.A = x;
     g.B = quantized ? l->weight_integer : l->weight;
     g.C = y;
-    g.s = quantized ? l->scale : nullptr;
+    g.s = QA ? out_scale : (quantized ? l->scale : nullptr);
     g.s_stride = l->per_channel ? 1 : 0;
     g.bias = quantized ? l->bias_integer : l->bias;
-    return launch_gemm<FWD>(g, act, (hipStream_t)stream, what);
+    g.prev = prev;
+    return launch_gemm<FWD, QA>(g, act, (hipStream_t)stream, what);
 }
 
+template <bool QA>
 int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, const float* y, const float* dy,
-               int64_t B, float* dx, float* dw, float* db, void* stream, const char* what) {
+               const float* prev, const float* out_scale, int64_t B, float* dx, float* dw, float* db, void* stream,
+               const char* what) {
     int rc = check_linear(l, quantized, what);
     if (rc) return rc;
     if ((rc = check_act(act, what))) return rc;
+    if (QA && (rc = check_qact(prev, out_scale, what))) return rc;
     if (B < 1 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
     if (!x || !dy || !dw || !db) return linear_error(DQRM_E_INVALID, "%s: null x / dy / dw / db", what);
     if (act != DQRM_ACT_NONE && !y)
@@ -435,8 +479,10 @@ int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, con
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g{};
     g.Y = act != DQRM_ACT_NONE ? y : nullptr;
-    g.s = quantized ? l->scale : nullptr;
+    g.s = QA ? out_scale : (quantized ? l->scale : nullptr);
     g.s_stride = l->per_channel ? 1 : 0;
+    g.prev = prev;
+    g.ws = l->scale;
     if (dx) {
         g.M = (int)B;
         g.N = l->in_features;
@@ -444,7 +490,7 @@ int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, con
         g.A = dy;
         g.B = quantized ? l->weight_integer : l->weight;
         g.C = dx;
-        if ((rc = launch_gemm<DX>(g, act, st, what))) return rc;
+        if ((rc = launch_gemm<DX, QA>(g, act, st, what))) return rc;
     }
     g.M = l->out_features;
     g.N = l->in_features;
@@ -453,30 +499,51 @@ int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, con
     g.B = x;
     g.C = dw;
     g.db = db;
-    return launch_gemm<DW>(g, act, st, what);
+    return launch_gemm<DW, QA>(g, act, st, what);
 }
 
 }  // namespace
 
 extern "C" {
 
+int dqrm_linear_wquant(const dqrm_linear* l, void* stream) {
+    return linear_wquant<false>(l, nullptr, nullptr, stream, "dqrm_linear_wquant");
+}
+
+int dqrm_linear_wquant_qact(const dqrm_linear* l, const float* prev, float* out_scale, void* stream) {
+    return linear_wquant<true>(l, prev, out_scale, stream, "dqrm_linear_wquant_qact");
+}
+
 int dqrm_linear_fwd(const dqrm_linear* l, int quantized, const float* x, int64_t B, float* y, void* stream) {
-    return linear_fwd(l, quantized, DQRM_ACT_NONE, x, B, y, stream, "dqrm_linear_fwd");
+    return linear_fwd<false>(l, quantized, DQRM_ACT_NONE, x, nullptr, nullptr, B, y, stream, "dqrm_linear_fwd");
 }
 
 int dqrm_linear_bwd(const dqrm_linear* l, int quantized, const float* x, const float* dy, int64_t B, float* dx,
                     float* dw, float* db, void* stream) {
-    return linear_bwd(l, quantized, DQRM_ACT_NONE, x, nullptr, dy, B, dx, dw, db, stream, "dqrm_linear_bwd");
+    return linear_bwd<false>(l, quantized, DQRM_ACT_NONE, x, nullptr, dy, nullptr, nullptr, B, dx, dw, db, stream,
+                             "dqrm_linear_bwd");
 }
 
 int dqrm_linear_fwd_act(const dqrm_linear* l, int quantized, int act, const float* x, int64_t B, float* y,
                         void* stream) {
-    return linear_fwd(l, quantized, act, x, B, y, stream, "dqrm_linear_fwd_act");
+    return linear_fwd<false>(l, quantized, act, x, nullptr, nullptr, B, y, stream, "dqrm_linear_fwd_act");
 }
 
 int dqrm_linear_bwd_act(const dqrm_linear* l, int quantized, int act, const float* x, const float* y,
                         const float* dy, int64_t B, float* dx, float* dw, float* db, void* stream) {
-    return linear_bwd(l, quantized, act, x, y, dy, B, dx, dw, db, stream, "dqrm_linear_bwd_act");
+    return linear_bwd<false>(l, quantized, act, x, y, dy, nullptr, nullptr, B, dx, dw, db, stream,
+                             "dqrm_linear_bwd_act");
+}
+
+int dqrm_linear_fwd_qact(const dqrm_linear* l, int act, const float* x, const float* prev, const float* out_scale,
+                         int64_t B, float* y, void* stream) {
+    return linear_fwd<true>(l, 1, act, x, prev, out_scale, B, y, stream, "dqrm_linear_fwd_qact");
+}
+
+int dqrm_linear_bwd_qact(const dqrm_linear* l, int act, const float* x, const float* y, const float* dy,
+                         const float* prev, const float* out_scale, int64_t B, float* dx, float* dw, float* db,
+                         void* stream) {
+    return linear_bwd<true>(l, 1, act, x, y, dy, prev, out_scale, B, dx, dw, db, stream, "dqrm_linear_bwd_qact");
 }
 
 }  // extern "C"

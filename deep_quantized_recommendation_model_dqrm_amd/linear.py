@@ -9,7 +9,7 @@ followed by ``set_param(nn.Linear)`` and call it as ``x, prev = layer(x, prev)``
 buffer names and state-dict keys of ``set_param`` (:70-97), ``__repr__`` (:64-68) and the
 ``(y, None)`` return of the weight-only forward (:209, :211):
 
-  * quantized forward (3 launches with per_channel, 4 without): dqrm_linear_wquant refreshes
+  * quantized forward (2 launches with per_channel, 3 without): dqrm_linear_wquant refreshes
     ``fc_scaling_factor``, ``weight_integer`` and ``bias_integer`` from the current weights
     (symmetric, the bias with the weight's scale), then dqrm_linear_fwd computes
     ``(x @ weight_integer.T + bias_integer) * fc_scaling_factor``;
@@ -25,8 +25,17 @@ activation that follows the layer in ``create_mlp`` into the same launches: dqrm
 applies it in the forward's epilogue and dqrm_linear_bwd_act multiplies ``dy`` by its derivative,
 read from the saved output, where the STE's scale is applied.
 
-Not built: ``QuantAct`` / activation quantization (``quantize_activation=True``, a
-``prev_act_scaling_factor``) and asymmetric weights (the reference raises there too).
+Activation quantization (``quantize_activation=True`` with a one-element
+``prev_act_scaling_factor`` p, from ``QuantAct`` or the layer before; q_m_n_q_g.py:150-161,
+:193-196) runs the same launch counts on dqrm_linear_wquant_qact / _fwd_qact / _bwd_qact: the bias
+is quantized with ``fc_scaling_factor * p``, which is also the ``correct_output_scale`` buffer
+([1, out_features] with per_channel, [1, 1] without, a fresh tensor per forward), the operand is
+``x / p`` and the layer returns ``(round(x/p @ weight_integer.T + bias_integer) *
+correct_output_scale, correct_output_scale)``. A per-channel ``correct_output_scale`` cannot be
+the next layer's p (more than one element): the reference fails there too.
+
+Not built: asymmetric weights (the reference raises there too) and a ``prev_act_scaling_factor``
+on a layer without ``quantize_activation`` (the drivers never pass one).
 """
 from __future__ import annotations
 
@@ -104,6 +113,52 @@ class _LinearFn(torch.autograd.Function):
                                                    db.data_ptr(), _stream_handle()),
                     "dqrm_linear_bwd_act")
         return dx, dw, db, None, None, None
+
+
+class MissingActScale(ValueError, NotImplementedError):
+    """quantize_activation=True without a prev_act_scaling_factor (the reference hits a NameError
+    there). A ValueError; also a NotImplementedError, which this call raised while the
+    activation-quantized path did not exist."""
+
+
+class _LinearQActFn(torch.autograd.Function):
+    """Autograd bridge over dqrm_linear_wquant_qact / _fwd_qact / _bwd_qact. ``cos`` is the fresh
+    correct_output_scale tensor the forward writes; the backward reads it, the saved ``prev`` and
+    the integers and fc_scaling_factor the layer's latest forward wrote."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, owner, act, prev, cos):
+        lib, c, st = owner._lib, owner._c_struct(), _stream_handle()
+        L.check(lib.dqrm_linear_wquant_qact(C.byref(c), prev.data_ptr(), cos.data_ptr(), st),
+                "dqrm_linear_wquant_qact")
+        y = torch.empty((x.shape[0], owner.out_features), dtype=torch.float32, device=x.device)
+        L.check(lib.dqrm_linear_fwd_qact(C.byref(c), act, x.data_ptr(), prev.data_ptr(), cos.data_ptr(), x.shape[0],
+                                         y.data_ptr(), st), "dqrm_linear_fwd_qact")
+        if act == L.DQRM_ACT_NONE:
+            ctx.save_for_backward(x, prev, cos)
+        else:
+            ctx.save_for_backward(x, prev, cos, y)
+        ctx.owner = owner
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, prev, cos, *ys = ctx.saved_tensors
+        owner = ctx.owner
+        dy = dy.contiguous()
+        B = x.shape[0]
+        dw = torch.empty_like(owner.weight)
+        db = torch.empty_like(owner.bias)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        if B == 0:
+            return dx, dw.zero_(), db.zero_(), None, None, None, None
+        L.check(owner._lib.dqrm_linear_bwd_qact(C.byref(owner._c_struct()), ctx.act, x.data_ptr(),
+                                                ys[0].data_ptr() if ys else None, dy.data_ptr(), prev.data_ptr(),
+                                                cos.data_ptr(), B, None if dx is None else dx.data_ptr(),
+                                                dw.data_ptr(), db.data_ptr(), _stream_handle()),
+                "dqrm_linear_bwd_qact")
+        return dx, dw, db, None, None, None, None
 
 
 class QuantLinear(nn.Module):
@@ -192,7 +247,8 @@ class QuantLinear(nn.Module):
 
     # ------------------------------------------------------------ forward
     def forward(self, x, prev_act_scaling_factor=None):
-        """(y, None), as the reference's weight-only QuantLinear returns."""
+        """(y, None), as the reference's weight-only QuantLinear returns; with quantize_activation
+        (y, correct_output_scale)."""
         if type(x) is tuple:
             prev_act_scaling_factor = x[1]
             x = x[0]
@@ -202,9 +258,21 @@ class QuantLinear(nn.Module):
                 raise Exception("For weight, we only support symmetric quantization.")
             if self.quant_mode != "symmetric":
                 raise ValueError("unknown quant mode: {}".format(self.quant_mode))
-            if self.quantize_activation or prev_act_scaling_factor is not None:
-                raise NotImplementedError("activation quantization (QuantAct, quantize_activation=True, "
-                                          "prev_act_scaling_factor) is not built")
+            if self.quantize_activation and prev_act_scaling_factor is None:
+                raise MissingActScale("QuantLinear(quantize_activation=True) needs a prev_act_scaling_factor "
+                                      "(QuantAct's act_scaling_factor or the previous layer's "
+                                      "correct_output_scale)")
+            if prev_act_scaling_factor is not None and not self.quantize_activation:
+                raise NotImplementedError("a prev_act_scaling_factor on a QuantLinear without "
+                                          "quantize_activation=True is not built (the reference's drivers never "
+                                          "pass one)")
+            if prev_act_scaling_factor is not None and (not isinstance(prev_act_scaling_factor, torch.Tensor)
+                                                        or prev_act_scaling_factor.numel() != 1):
+                got = (tuple(prev_act_scaling_factor.shape) if isinstance(prev_act_scaling_factor, torch.Tensor)
+                       else type(prev_act_scaling_factor).__name__)
+                raise ValueError(f"prev_act_scaling_factor must be a tensor of ONE element (got {got}); a "
+                                 "per-channel correct_output_scale cannot feed the next layer, in the reference "
+                                 "either")
             if self.bias_bit is None:
                 raise TypeError("QuantLinear quantizes its bias: bias_bit must be an int")
         if "weight" not in self._parameters:
@@ -218,8 +286,21 @@ class QuantLinear(nn.Module):
             self._scale_buffer()
         if x.device.index != torch.cuda.current_device():
             with torch.cuda.device(x.device):
-                return _LinearFn.apply(x, self.weight, self.bias, self, quantized, act), None
-        return _LinearFn.apply(x, self.weight, self.bias, self, quantized, act), None
+                return self._run_layer(x, quantized, act, prev_act_scaling_factor)
+        return self._run_layer(x, quantized, act, prev_act_scaling_factor)
+
+    def _run_layer(self, x, quantized, act, prev):
+        if not (quantized and self.quantize_activation):
+            return _LinearFn.apply(x, self.weight, self.bias, self, quantized, act), None
+        if prev.dtype != torch.float32 or prev.device != x.device:
+            raise ValueError(f"prev_act_scaling_factor must be float32 on the input's device (got {prev.dtype} on "
+                             f"{prev.device})")
+        # [1, O] / [1, 1] as q_m_n_q_g.py:161 leaves it; fresh per forward, so the scale the next
+        # layer saved for its backward is never overwritten
+        cos = torch.empty((1, self.out_features if self.per_channel else 1), dtype=torch.float32, device=x.device)
+        y = _LinearQActFn.apply(x, self.weight, self.bias, self, act, prev.detach(), cos)
+        self._buffers["correct_output_scale"] = cos
+        return y, cos
 
 
 __all__ = ["QuantLinear"]

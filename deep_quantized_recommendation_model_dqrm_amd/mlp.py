@@ -82,12 +82,15 @@ def unfuse_activations(layers) -> int:
     return restored
 
 
-def create_mlp(ln, sigmoid_layer, weight_bit=4, full_precision_flag=False, per_channel=False, fused=True):
+def create_mlp(ln, sigmoid_layer, weight_bit=4, full_precision_flag=False, per_channel=False, fused=True,
+               quantize_activation=False):
     """DLRM_Net.create_mlp with every layer a package QuantLinear (bias_bit = weight_bit). Layer i
     maps ln[i] -> ln[i + 1] features; its weight is drawn from N(0, 2 / (m + n)) as an [m, n]
     array and then its bias from N(0, 1 / m), both from numpy's global generator and cast to
     float32, in that order, layer after layer (the reference's initialisation and draw sequence).
-    A Sigmoid follows layer ``sigmoid_layer``, a ReLU every other. fused: fuse_activations."""
+    A Sigmoid follows layer ``sigmoid_layer``, a ReLU every other. fused: fuse_activations.
+    quantize_activation is passed to every layer (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:280,
+    :323): the stack then needs apply_mlp's prev_act_scaling_factor, from a QuantAct."""
     ln = [int(v) for v in np.asarray(ln).reshape(-1)]
     layers = nn.ModuleList()
     for i, (n, m) in enumerate(zip(ln[:-1], ln[1:])):
@@ -97,7 +100,7 @@ def create_mlp(ln, sigmoid_layer, weight_bit=4, full_precision_flag=False, per_c
         lin.weight.data = torch.from_numpy(W)
         lin.bias.data = torch.from_numpy(b)
         q = QuantLinear(weight_bit=weight_bit, bias_bit=weight_bit, full_precision_flag=full_precision_flag,
-                        per_channel=per_channel)
+                        per_channel=per_channel, quantize_activation=quantize_activation)
         q.set_param(lin)
         layers.append(q)
         layers.append(nn.Sigmoid() if i == sigmoid_layer else nn.ReLU())
@@ -106,10 +109,11 @@ def create_mlp(ln, sigmoid_layer, weight_bit=4, full_precision_flag=False, per_c
     return layers
 
 
-def apply_mlp(x, layers):
-    """DLRM_Net.apply_mlp's loop: a QuantLinear is called with, and returns, the activation scale
-    beside the tensor; any other module maps the tensor."""
-    prev_act_scaling_factor = None
+def apply_mlp(x, layers, prev_act_scaling_factor=None):
+    """DLRM_Net.apply_mlp's loop (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:550, :592): a
+    QuantLinear is called with, and returns, the activation scale beside the tensor; any other
+    module maps the tensor. prev_act_scaling_factor: the scale of the QuantAct before the stack
+    (layers built with quantize_activation), None for weight-only layers."""
     for layer in layers:
         if isinstance(layer, QuantLinear):
             x, prev_act_scaling_factor = layer(x, prev_act_scaling_factor)

@@ -22,7 +22,8 @@ state-dict keys (:258-280, :288), and its semantics (:317-398):
                                sgd_quantized_gradients_parallel_comm.grad_update_parallel_comm.
 
 ``QuantLinear`` (the MLP layers, :20-211) lives in ``linear.py`` and is re-exported here, where
-the reference's drivers import it from.
+the reference's drivers import it from; so does ``QuantAct`` (activation quantization,
+:541-725), in ``act.py``.
 
 ``QuantEmbeddingBagCollection`` is the fused T-table form used to replace the per-table
 loop of DLRM_Net.apply_emb (dlrm_s_pytorch_single_gpu.py:609-674): one launch per step for
@@ -40,6 +41,7 @@ from torch import nn
 
 from . import _lib as L
 from .linear import QuantLinear  # the reference defines it in this module (q_m_n_q_g.py:20-211)
+from .act import QuantAct  # likewise (q_m_n_q_g.py:541-725)
 from .tables import EmbeddingTableSet, LookupBatch
 
 
@@ -630,6 +632,6 @@ class QuantEmbeddingBagCollection(_QuantEmbeddingBase):
         return out
 
 
-__all__ = ["QuantLinear", "QuantEmbeddingBagTwo", "QuantEmbeddingBagCollection", "set_default_grad_mode", "set_sparse_grad_form",
+__all__ = ["QuantLinear", "QuantAct", "QuantEmbeddingBagTwo", "QuantEmbeddingBagCollection", "set_default_grad_mode", "set_sparse_grad_form",
            "set_fused_optimizer_step",
            "set_error_check_interval", "set_pooling_one_inputs", "consolidate_tables", "can_consolidate"]

@@ -73,7 +73,12 @@ extern "C" {
                                   dqrm_interact_out_features, dqrm_interact_scale,
                                   dqrm_interact_fwd, dqrm_interact_bwd;
                                   likewise within 12: the MLP's activation fused into the layer,
-                                  DQRM_ACT_*, dqrm_linear_fwd_act, dqrm_linear_bwd_act */
+                                  DQRM_ACT_*, dqrm_linear_fwd_act, dqrm_linear_bwd_act;
+                                  likewise within 12: activation quantization, dqrm_act_quant
+                                  (QuantAct): dqrm_act_quant_workspace_bytes, dqrm_act_quant_fwd,
+                                  dqrm_act_quant_bwd; and the layer's integer-activation branch:
+                                  dqrm_linear_wquant_qact, dqrm_linear_fwd_qact,
+                                  dqrm_linear_bwd_qact */
 
 /* status codes */
 #define DQRM_OK            0
@@ -647,6 +652,94 @@ int dqrm_linear_fwd_act(const dqrm_linear* layer, int quantized, int act,
 int dqrm_linear_bwd_act(const dqrm_linear* layer, int quantized, int act,
                         const float* x, const float* y, const float* dy, int64_t B,
                         float* dx, float* dw, float* db, void* stream);
+
+/* QuantLinear's integer-activation branch (quantize_activation with a prev_act_scaling_factor,
+ * q_m_n_q_g.py:150-161, :193-196), on the same kernels as the calls above and under the same
+ * arithmetic rules. Two more device pointers:
+ *   prev       one float, p: the previous activation scale (QuantAct's act_scaling_factor, or the
+ *              out_scale of the layer before)
+ *   out_scale  [O] with per_channel, [1] otherwise: cos[o] = scale[o] * p, the reference's
+ *              bias_scaling_factor / correct_output_scale
+ * p has ONE element. A per-channel cos of layer i cannot be the prev of layer i+1: the reference
+ * breaks there too (`fc_scaling_factor.view(1,-1) * prev.view(1,-1)` does not broadcast [1,O']
+ * against [1,O]). Quantized only; there is no full-precision form.
+ *
+ * dqrm_linear_wquant_qact: scale and weight_integer as dqrm_linear_wquant writes them, bit for
+ * bit, and
+ *   out_scale[o]    = scale[o] * p
+ *   bias_integer[o] = clamp(round(1/out_scale[o] * b[o] + 0), -nb-1, nb)            (:150-154)
+ * One launch with per_channel, two without.
+ *
+ * dqrm_linear_fwd_qact, x [B][K] -> y [B][O], one launch:
+ *   acc    = chain over k of (x[b,k] / p) * weight_integer[o,k]     (x / p formed on load, :160)
+ *   y[b,o] = act(rintf(acc + bias_integer[o]) * cos[o])             (ste_round(F.linear) * cos, :194-196)
+ * with act as in dqrm_linear_fwd_act.
+ *
+ * dqrm_linear_bwd_qact, d = dy * act'(y) as in dqrm_linear_bwd_act, g[b,o] = d[b,o] * cos[o]
+ * (ste_round passes g through):
+ *   dx[b,k] = (chain over o of g[b,o] * weight_integer[o,k]) / p     (dx == NULL: skipped)
+ *   dw[o,k] = (chain over b of g[b,o] * (x[b,k] / p)) / scale[o]
+ *   db[o]   = (chain over b of g[b,o]) / cos[o]
+ * Two launches, one when dx == NULL.
+ *
+ * DQRM_E_INVALID before any device work: everything dqrm_linear_wquant / _fwd_act / _bwd_act
+ * reject for a quantized layer, and a null prev / out_scale. B == 0 in the forward: DQRM_OK, no
+ * launch. */
+int dqrm_linear_wquant_qact(const dqrm_linear* layer, const float* prev, float* out_scale, void* stream);
+int dqrm_linear_fwd_qact(const dqrm_linear* layer, int act, const float* x, const float* prev,
+                         const float* out_scale, int64_t B, float* y, void* stream);
+int dqrm_linear_bwd_qact(const dqrm_linear* layer, int act, const float* x, const float* y, const float* dy,
+                         const float* prev, const float* out_scale, int64_t B,
+                         float* dx, float* dw, float* db, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * QuantAct: fake-quantized activations with a running range (quantization_supp/
+ * quant_modules_not_quantize_grad.py:541-725), csrc/dqrm_act.hip. Symmetric, one scale for the
+ * tensor, act_percentile == 0. Every `*`, `/` and `+` below is one separately rounded f32
+ * operation; min and max are exact and order-independent; nothing is read back to the host (the
+ * reference's `if self.x_min == self.x_max` is taken on the device). x finite.
+ *
+ * dqrm_act_quant_fwd, x [numel] -> y [numel]:
+ *   running_stat != 0 (QuantAct.forward:653-678), bmin = min(x), bmax = max(x):
+ *     x_min == x_max:   x_min = x_min + bmin;  x_max = x_max + bmax      (an add, as written there)
+ *     momentum == -1:   x_min = min(x_min, bmin);  x_max = max(x_max, bmax)
+ *     otherwise:        x_min = x_min * momentum + bmin * one_minus_momentum;  x_max likewise
+ *   n = 2^(activation_bit-1) - 1
+ *   scale[0] = max(max(|x_min|, |x_max|), 1e-8) / n                      (quant_utils.py:196-220)
+ *   y = clamp(rintf(1/scale * x + 0), -n-1, n) * scale          (quant_utils.py:101, :343; :694, :722-723)
+ * y == NULL with running_stat: the range update alone (full_precision_flag), scale untouched.
+ * Launches: at most THREE. With running_stat, numel > 16384: per-workgroup min / max into the
+ * workspace, then one workgroup that reduces them and updates the range, then the elementwise
+ * pass (3); numel <= 16384: the one workgroup reads x itself (2); without running_stat: the
+ * elementwise pass alone (1). The range update is a launch of a single workgroup between the
+ * other two, so no workgroup reads a half-updated range.
+ * workspace: dqrm_act_quant_workspace_bytes(numel) bytes of device memory, 4-byte aligned, contents
+ * irrelevant; may be NULL when that is 0 or running_stat is 0.
+ *
+ * dqrm_act_quant_bwd: dx = (dy * scale[0]) / scale[0]  (quant_utils.py:349-363 under the
+ * `* correct_output_scale` of :723), one launch; a caller whose input needs no gradient does
+ * not call it.
+ *
+ * DQRM_E_INVALID before any device work: a null struct, activation_bit outside 2..32, null
+ * x_min / x_max / scale, negative numel, null x (or y without running_stat), a null workspace
+ * where one is needed; null scale / dy / dx in the backward. numel == 0: DQRM_OK, no launch, the
+ * range left alone.
+ * ------------------------------------------------------------------------------ */
+typedef struct dqrm_act_quant {
+    int32_t activation_bit;    /* 2..32 */
+    int32_t running_stat;      /* update x_min / x_max from this batch */
+    float momentum;            /* act_range_momentum; -1: running min / max */
+    float one_minus_momentum;  /* (float)(1.0 - (double)act_range_momentum): what torch multiplies an
+                                  f32 tensor with for the Python scalar `1 - momentum` */
+    float* x_min;              /* [1] */
+    float* x_max;              /* [1] */
+    float* scale;              /* [1]: act_scaling_factor */
+} dqrm_act_quant;
+
+int64_t dqrm_act_quant_workspace_bytes(int64_t numel);
+int dqrm_act_quant_fwd(const dqrm_act_quant* q, const float* x, int64_t numel, float* y, void* workspace,
+                       void* stream);
+int dqrm_act_quant_bwd(const float* scale, const float* dy, int64_t numel, float* dx, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * DotInteraction: DLRM_Net.interact_features, arch_interaction_op "dot"

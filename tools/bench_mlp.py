@@ -172,7 +172,7 @@ def layer_times(path):
     t = collections.defaultdict(list)
     with open(path) as f:
         for r in csv.DictReader(f):
-            m = re.search(r"k_linear_gemm<(\d), (\d), (\d)>", r["Kernel_Name"])
+            m = re.search(r"k_linear_gemm<(\d), (\d), (\d)(?:, false)?>", r["Kernel_Name"])  # not the QA ones
             if m:
                 wt, mode, act = map(int, m.groups())
                 grid = (int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"]), int(r["Grid_Size_Y"]))
