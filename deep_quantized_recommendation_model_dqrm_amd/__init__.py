@@ -9,6 +9,9 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
                                                                 fused into the layers' kernels)
   * ``DLRM_Net.interact_features``                               (``DotInteraction``: the dot interaction,
                                                                 plain or 16-bit fake-quantized, fused)
+  * ``DLRM_Net.forward``'s clamp and ``loss_fn_wrap``            (``DLRMLoss``: BCE / MSE / weighted BCE with
+                                                                its gradient in one launch, a mean whose
+                                                                bits depend on the batch size alone)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
@@ -26,6 +29,7 @@ from .linear import QuantLinear
 from .act import QuantAct
 from .mlp import FusedActivation, apply_mlp, create_mlp, fuse_activations, unfuse_activations
 from .interaction import DotInteraction, interact_features
+from .loss import DLRMLoss, loss_fn_wrap
 from . import quantized_ops
 
 __all__ = [
@@ -53,6 +57,8 @@ __all__ = [
     "FusedActivation",
     "DotInteraction",
     "interact_features",
+    "DLRMLoss",
+    "loss_fn_wrap",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

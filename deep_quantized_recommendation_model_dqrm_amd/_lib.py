@@ -60,6 +60,11 @@ DQRM_ACT_NONE = 0
 DQRM_ACT_RELU = 1
 DQRM_ACT_SIGMOID = 2
 
+DQRM_LOSS_BCE = 0
+DQRM_LOSS_MSE = 1
+DQRM_LOSS_WBCE = 2
+DQRM_LOSS_MAX_BATCH = 1 << 20  # dqrm_loss_fwd's one workgroup
+
 DQRM_ABI_VERSION = 12  # include/dqrm.h
 DQRM_PRESUM_MAX_LOOKUPS = 2048
 
@@ -110,6 +115,8 @@ EXPORTED_SYMBOLS = (
     "dqrm_act_quant_workspace_bytes",
     "dqrm_act_quant_fwd",
     "dqrm_act_quant_bwd",
+    "dqrm_loss_fwd",
+    "dqrm_loss_bwd",
     "dqrm_interact_out_features",
     "dqrm_interact_scale",
     "dqrm_interact_fwd",
@@ -228,6 +235,19 @@ class ActQuant(C.Structure):
         ("x_min", C.c_void_p),
         ("x_max", C.c_void_p),
         ("scale", C.c_void_p),
+    ]
+
+
+class Loss(C.Structure):
+    """Mirror of ``dqrm_loss`` (include/dqrm.h)."""
+
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("clamp", C.c_int32),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("num_weights", C.c_int32),
+        ("weights", C.c_void_p),
     ]
 
 
@@ -393,6 +413,8 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_act_quant_workspace_bytes": (C.c_int64, [C.c_int64]),
         "dqrm_act_quant_fwd": (C.c_int, [AQ, P, C.c_int64, P, P, P]),
         "dqrm_act_quant_bwd": (C.c_int, [P, P, C.c_int64, P, P]),
+        "dqrm_loss_fwd": (C.c_int, [C.POINTER(Loss), P, P, C.c_int64, P, P, P, P, P]),
+        "dqrm_loss_bwd": (C.c_int, [P, P, C.c_int64, P, P]),
         "dqrm_interact_out_features": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
         "dqrm_interact_scale": (C.c_int, [IA, P, P, C.c_int64, P, P]),
         "dqrm_interact_fwd": (C.c_int, [IA, P, P, C.c_int64, P, P, P]),

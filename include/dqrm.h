@@ -78,7 +78,9 @@ extern "C" {
                                   (QuantAct): dqrm_act_quant_workspace_bytes, dqrm_act_quant_fwd,
                                   dqrm_act_quant_bwd; and the layer's integer-activation branch:
                                   dqrm_linear_wquant_qact, dqrm_linear_fwd_qact,
-                                  dqrm_linear_bwd_qact */
+                                  dqrm_linear_bwd_qact;
+                                  likewise within 12: the loss head, dqrm_loss (DLRMLoss),
+                                  DQRM_LOSS_*: dqrm_loss_fwd, dqrm_loss_bwd */
 
 /* status codes */
 #define DQRM_OK            0
@@ -740,6 +742,60 @@ int64_t dqrm_act_quant_workspace_bytes(int64_t numel);
 int dqrm_act_quant_fwd(const dqrm_act_quant* q, const float* x, int64_t numel, float* y, void* workspace,
                        void* stream);
 int dqrm_act_quant_bwd(const float* scale, const float* dy, int64_t numel, float* dx, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * DLRMLoss: the model's head, csrc/dqrm_loss.hip. DLRM_Net.forward's
+ * `torch.clamp(p, min=loss_threshold, max=1.0 - loss_threshold)`
+ * (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:837-839, :877-879) and loss_fn_wrap (:193-212):
+ * BCELoss / MSELoss(reduction="mean"), or for "wbce" loss_ws[T.long()] * BCELoss(reduction="none")
+ * and .mean(). All f32, every operation below rounded on its own, nothing read back to the host.
+ *
+ * Per sample, p the top MLP's output and t the target (B contiguous floats each):
+ *   z = clamp ? min(max(p, lo), hi) : p            NaN propagating (a caller passes
+ *       lo = (float)loss_threshold, hi = (float)(1.0 - (double)loss_threshold): what torch.clamp
+ *       compares an f32 tensor with for those Python scalars; clamp only if 0 < threshold < 1)
+ *   DQRM_LOSS_BCE   l = (t - 1) * max(log1pf(-z), -100) - t * max(logf(z), -100)      w = 1
+ *                   d = (z - t) / max((1 - z) * z, 1e-12f)
+ *   DQRM_LOSS_MSE   l = (z - t) * (z - t)           d = 2 * (z - t)                       w = 1
+ *   DQRM_LOSS_WBCE  BCE's l and d, w = weights[(int64)t]; a class outside [0, num_weights) reads
+ *                   no memory: w = NaN, so that sample's term and gradient and the loss are NaN.
+ *                   (The reference keeps loss_ws in float64 and its wbce loss is float64; here
+ *                   the weights are f32 and so is the loss.)
+ *   Both max() keep a NaN. z outside [0, 1] is outside BCELoss's domain (torch asserts): NaN here.
+ *   terms[i] = w * l
+ *   g[i]     = (w * d) / (float)B;  0 where the clamp cut (p < lo or p > hi: torch's bounds are
+ *              inclusive); a NaN p gives NaN
+ *   loss[0]  = S / (float)B, S the sum of the terms in an order that is a function of B alone:
+ *              slot s = i mod 256 starts at +0.0f and adds its terms i = s, s + 256, ... in
+ *              ascending i; the slots are folded with slot[s] += slot[s + stride] for
+ *              stride = 128, 64, ..., 1; S = slot[0]. Plain f32 adds. The bits of the loss do
+ *              not depend on the grid, the device or the stream.
+ * dqrm_loss_fwd is exactly ONE launch (one workgroup of 256 threads, thread s owning slot s) and
+ * no memset: the kernel writes loss[0] itself. g NULL: an inference-only loss. z (the clamped
+ * prediction, DLRM_Net.forward's return value) and terms (reduction="none") may be NULL.
+ *
+ * dqrm_loss_bwd: dp = go[0] * g, one launch; go is the 0-dim upstream gradient in device memory.
+ * A caller whose p needs no gradient does not call it.
+ *
+ * DQRM_E_INVALID before any device work: a null struct, an unknown kind, DQRM_LOSS_WBCE without
+ * weights (NULL or num_weights < 1), B < 1 or B > 2^20 (the one-workgroup forward's limit),
+ * null p / t / loss; null g / go / dp in the backward.
+ * ------------------------------------------------------------------------------ */
+enum { DQRM_LOSS_BCE = 0, DQRM_LOSS_MSE = 1, DQRM_LOSS_WBCE = 2 };
+
+typedef struct dqrm_loss {
+    int32_t kind;          /* DQRM_LOSS_BCE / _MSE / _WBCE */
+    int32_t clamp;         /* 0 / 1 */
+    float lo, hi;          /* the clamp's bounds (ignored when clamp == 0) */
+    int32_t num_weights;   /* wbce: entries of weights */
+    const float* weights;  /* device [num_weights], wbce (ignored otherwise) */
+} dqrm_loss;
+
+int dqrm_loss_fwd(const dqrm_loss* cfg, const float* p, const float* t, int64_t B,
+                  float* loss /*[1]*/, float* g /*[B], nullable*/,
+                  float* z /*[B], nullable*/, float* terms /*[B], nullable*/,
+                  void* stream);
+int dqrm_loss_bwd(const float* g, const float* go, int64_t B, float* dp, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * DotInteraction: DLRM_Net.interact_features, arch_interaction_op "dot"
