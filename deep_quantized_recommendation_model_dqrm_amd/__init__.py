@@ -27,7 +27,7 @@ from . import quant_modules_not_quantize_grad, sgd_quantized_gradients, sgd_quan
 from .quant_modules_not_quantize_grad import QuantEmbeddingBagCollection, QuantEmbeddingBagTwo
 from .linear import QuantLinear
 from .act import QuantAct
-from .mlp import FusedActivation, apply_mlp, create_mlp, fuse_activations, unfuse_activations
+from .mlp import FusedActivation, MLPStack, apply_mlp, create_mlp, fuse_activations, unfuse_activations
 from .interaction import DotInteraction, interact_features
 from .loss import DLRMLoss, loss_fn_wrap
 from . import quantized_ops
@@ -55,6 +55,7 @@ __all__ = [
     "fuse_activations",
     "unfuse_activations",
     "FusedActivation",
+    "MLPStack",
     "DotInteraction",
     "interact_features",
     "DLRMLoss",

@@ -60,6 +60,10 @@ DQRM_ACT_NONE = 0
 DQRM_ACT_RELU = 1
 DQRM_ACT_SIGMOID = 2
 
+DQRM_MLP_MAX_LAYERS = 16
+DQRM_MLP_FRESH = 1
+DQRM_MLP_REQUANT = 1
+
 DQRM_LOSS_BCE = 0
 DQRM_LOSS_MSE = 1
 DQRM_LOSS_WBCE = 2
@@ -112,6 +116,11 @@ EXPORTED_SYMBOLS = (
     "dqrm_linear_wquant_qact",
     "dqrm_linear_fwd_qact",
     "dqrm_linear_bwd_qact",
+    "dqrm_mlp_fwd",
+    "dqrm_mlp_bwd_scratch_bytes",
+    "dqrm_mlp_bwd",
+    "dqrm_mlp_sgd_workspace_bytes",
+    "dqrm_mlp_sgd",
     "dqrm_act_quant_workspace_bytes",
     "dqrm_act_quant_fwd",
     "dqrm_act_quant_bwd",
@@ -224,6 +233,18 @@ class Linear(C.Structure):
     ]
 
 
+class MLP(C.Structure):
+    """Mirror of ``dqrm_mlp`` (include/dqrm.h): host arrays of L layers."""
+
+    _fields_ = [
+        ("num_layers", C.c_int32),
+        ("reserved", C.c_int32),
+        ("layers", C.POINTER(Linear)),
+        ("quantized", C.POINTER(C.c_int32)),
+        ("act", C.POINTER(C.c_int32)),
+    ]
+
+
 class ActQuant(C.Structure):
     """Mirror of ``dqrm_act_quant`` (include/dqrm.h)."""
 
@@ -319,6 +340,8 @@ def load(path: str | None = None) -> C.CDLL:
     LN = C.POINTER(Linear)
     IA = C.POINTER(Interact)
     AQ = C.POINTER(ActQuant)
+    ML = C.POINTER(MLP)
+    PP = C.POINTER(C.c_void_p)  # a host array of device pointers
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -410,6 +433,11 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_linear_wquant_qact": (C.c_int, [LN, P, P, P]),
         "dqrm_linear_fwd_qact": (C.c_int, [LN, C.c_int, P, P, P, C.c_int64, P, P]),
         "dqrm_linear_bwd_qact": (C.c_int, [LN, C.c_int, P, P, P, P, P, C.c_int64, P, P, P, P]),
+        "dqrm_mlp_fwd": (C.c_int, [ML, C.c_uint32, P, C.c_int64, PP, P]),
+        "dqrm_mlp_bwd_scratch_bytes": (C.c_size_t, [ML, C.c_int64]),
+        "dqrm_mlp_bwd": (C.c_int, [ML, P, PP, P, C.c_int64, P, PP, PP, P, C.c_size_t, P]),
+        "dqrm_mlp_sgd_workspace_bytes": (C.c_size_t, [ML]),
+        "dqrm_mlp_sgd": (C.c_int, [ML, C.c_uint32, PP, PP, PP, C.c_float, P, C.c_size_t, P]),
         "dqrm_act_quant_workspace_bytes": (C.c_int64, [C.c_int64]),
         "dqrm_act_quant_fwd": (C.c_int, [AQ, P, C.c_int64, P, P, P]),
         "dqrm_act_quant_bwd": (C.c_int, [P, P, C.c_int64, P, P]),

@@ -1,0 +1,357 @@
+// dqrm_mlp.hip — a whole MLP stack per host call, and the stack's SGD update fused with the
+// requantization the next forward needs, gfx950.
+//
+// dqrm_mlp_fwd / dqrm_mlp_bwd hold no GEMM code: they validate the whole stack and then call the
+// per-layer exports of dqrm_linear.hip (dqrm_linear_wquant, dqrm_linear_fwd_act,
+// dqrm_linear_bwd_act) in the order a layer-by-layer caller would, so their bits are those calls'
+// bits by construction. What they save is the host's work per layer.
+//
+// dqrm_mlp_sgd is the new kernel. Reference (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM
+// @ 2024-10-24): sgd_quantized_gradients_parallel_comm.py:642-646 (the MLP branch of
+// weight_update_parallel_comm) and the quantization half of QuantLinear.forward
+// (quantization_supp/quant_modules_not_quantize_grad.py:121-154), i.e. what dqrm_dense_update and
+// dqrm_linear_wquant compute, in their order of operations:
+//     W[o,k] = W[o,k] + (nlr * dw[o,k]) [* gscale[o]]
+//     s[o]   = fmaxf(max_k |W[o,k]|, 1e-8f) / n;  wi = clamp(rintf(1/s * W + 0));  bi likewise
+// One wave per weight row, the rows of ALL layers in one grid: a wave finds its (layer, row) from
+// the prefix of row counts in the kernel arguments (the layer descriptors travel by value, hence
+// DQRM_MLP_MAX_LAYERS). A per-channel row is finished by the wave that updated it. A per-tensor
+// layer needs the maximum over all its rows: launch 1 leaves every row's max|W| in the workspace,
+// launch 2 has every wave of the layer reduce those row maxima itself (a maximum does not depend
+// on the order it is taken in) and write its row's integers. No atomics, no memset, no workgroup
+// waits on another.
+//
+// Compiled with -ffp-contract=off: `nlr * dw`, `* gscale` and `W + ...` are separately rounded.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdarg.h>
+#include <math.h>
+
+#include "../../include/dqrm.h"
+
+extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int SWG = 256;            // threads per workgroup
+constexpr int SRPW = SWG / WAVE;    // weight rows per workgroup (one per wave)
+
+int mlp_error(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return dqrm_internal_set_error(code, buf);
+}
+
+#define MHIP_TRY(expr)                                                                     \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return mlp_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
+    } while (0)
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
+    return v;
+}
+
+// dqrm_linear.hip's quant1: torch.round (half to even) == rintf; clamp to [lo, hi]
+__device__ __forceinline__ float quant1(float w, float rcp, float lo, float hi) {
+    const float q = rintf(rcp * w + 0.0f);
+    return fminf(fmaxf(q, lo), hi);
+}
+
+enum { UPDATE_ONLY = 0, REQUANT_ROWS = 1, REQUANT_TENSOR = 2 };
+
+struct SgdLayer {
+    float* W;             // [out][in], updated in place
+    float* b;             // [out]
+    const float* dw;
+    const float* db;
+    const float* gs;      // [out + 1] gradient scales (rows, then the bias), or null
+    float* wi;
+    float* bi;
+    float* scale;
+    float n;              // 2^(weight_bit-1) - 1
+    float wlo, whi;       // weight clamp
+    float blo, bhi;       // bias clamp
+    int out, in;
+    int row0;             // the layer's first row in the grid
+    int mode;             // UPDATE_ONLY / REQUANT_ROWS / REQUANT_TENSOR
+};
+
+struct SgdArgs {
+    SgdLayer layer[DQRM_MLP_MAX_LAYERS];
+    int num_layers;
+    int total_rows;
+    float nlr;            // -lr
+    float* rowmax;        // [total_rows] workspace (REQUANT_TENSOR layers only)
+};
+
+// the wave's row and its layer (both wave-uniform, so the descriptor is read with scalar loads)
+__device__ __forceinline__ bool locate(const SgdArgs& a, int& row, int& l) {
+    row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * SRPW + threadIdx.x / WAVE));
+    if (row >= a.total_rows) return false;
+    l = 0;
+    while (l + 1 < a.num_layers && row >= a.layer[l + 1].row0) ++l;
+    return true;
+}
+
+// Launch 1: the update of one weight row and its bias element; a per-channel row's scale and
+// integers; a per-tensor row's max|W| into the workspace.
+__global__ void __launch_bounds__(SWG) k_mlp_sgd(SgdArgs a) {
+    int row, l;
+    if (!locate(a, row, l)) return;
+    const SgdLayer& d = a.layer[l];
+    const int o = row - d.row0, lane = threadIdx.x % WAVE, in = d.in;
+    float* w = d.W + (int64_t)o * in;
+    const float* __restrict__ g = d.dw + (int64_t)o * in;
+    const float nlr = a.nlr;
+    float m = 0.0f, bv = 0.0f;
+    if (d.gs != nullptr) {
+        const float sc = d.gs[o];
+        for (int k = lane; k < in; k += WAVE) {
+            const float v = w[k] + (nlr * g[k]) * sc;
+            w[k] = v;
+            m = fmaxf(m, fabsf(v));
+        }
+        if (lane == 0) d.b[o] = bv = d.b[o] + (nlr * d.db[o]) * d.gs[d.out];
+    } else {
+        for (int k = lane; k < in; k += WAVE) {
+            const float v = w[k] + nlr * g[k];
+            w[k] = v;
+            m = fmaxf(m, fabsf(v));
+        }
+        if (lane == 0) d.b[o] = bv = d.b[o] + nlr * d.db[o];
+    }
+    if (d.mode == UPDATE_ONLY) return;
+    m = wave_max(m);
+    if (d.mode == REQUANT_TENSOR) {
+        if (lane == 0) a.rowmax[row] = m;
+        return;
+    }
+    const float s = fmaxf(m, 1e-8f) / d.n;
+    const float rcp = 1.0f / s;
+    float* __restrict__ wi = d.wi + (int64_t)o * in;
+    for (int k = lane; k < in; k += WAVE) wi[k] = quant1(w[k], rcp, d.wlo, d.whi);  // the lane's own stores
+    if (lane == 0) {
+        d.scale[o] = s;
+        d.bi[o] = quant1(bv, rcp, d.blo, d.bhi);
+    }
+}
+
+// Launch 2 (only when a quantized layer is per tensor): every wave of such a layer takes the
+// maximum over the layer's row maxima and writes its row's integers; row 0 also writes scale[0].
+__global__ void __launch_bounds__(SWG) k_mlp_requant_tensor(SgdArgs a) {
+    int row, l;
+    if (!locate(a, row, l)) return;
+    const SgdLayer& d = a.layer[l];
+    if (d.mode != REQUANT_TENSOR) return;
+    const int o = row - d.row0, lane = threadIdx.x % WAVE, in = d.in;
+    const float* __restrict__ rm = a.rowmax + d.row0;
+    float m = 0.0f;
+    for (int r = lane; r < d.out; r += WAVE) m = fmaxf(m, rm[r]);
+    m = wave_max(m);
+    const float s = fmaxf(m, 1e-8f) / d.n;
+    const float rcp = 1.0f / s;
+    const float* __restrict__ w = d.W + (int64_t)o * in;
+    float* __restrict__ wi = d.wi + (int64_t)o * in;
+    for (int k = lane; k < in; k += WAVE) wi[k] = quant1(w[k], rcp, d.wlo, d.whi);
+    if (lane == 0) {
+        d.bi[o] = quant1(d.b[o], rcp, d.blo, d.bhi);
+        if (o == 0) d.scale[0] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------ validation
+// dqrm_linear.hip's check_linear, per layer, and the stack's own fields
+int check_stack(const dqrm_mlp* m, const char* what) {
+    if (!m) return mlp_error(DQRM_E_INVALID, "%s: null stack", what);
+    if (m->num_layers < 1 || m->num_layers > DQRM_MLP_MAX_LAYERS)
+        return mlp_error(DQRM_E_INVALID, "%s: num_layers must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS,
+                         m->num_layers);
+    if (!m->layers || !m->quantized || !m->act)
+        return mlp_error(DQRM_E_INVALID, "%s: null layers / quantized / act array", what);
+    for (int i = 0; i < m->num_layers; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        if (l->in_features < 1 || l->out_features < 1)
+            return mlp_error(DQRM_E_INVALID, "%s: layer %d: in_features / out_features must be positive (got %d / %d)",
+                             what, i, l->in_features, l->out_features);
+        if (i > 0 && l->in_features != m->layers[i - 1].out_features)
+            return mlp_error(DQRM_E_INVALID, "%s: layer %d: in_features %d does not match layer %d's out_features %d",
+                             what, i, l->in_features, i - 1, m->layers[i - 1].out_features);
+        if (!l->weight || !l->bias) return mlp_error(DQRM_E_INVALID, "%s: layer %d: null weight / bias", what, i);
+        if (m->act[i] < DQRM_ACT_NONE || m->act[i] > DQRM_ACT_SIGMOID)
+            return mlp_error(DQRM_E_INVALID, "%s: layer %d: act must be DQRM_ACT_NONE, _RELU or _SIGMOID (got %d)",
+                             what, i, m->act[i]);
+        if (m->quantized[i]) {
+            if (l->weight_bit < 2 || l->weight_bit > 32 || l->bias_bit < 2 || l->bias_bit > 32)
+                return mlp_error(DQRM_E_INVALID, "%s: layer %d: weight_bit / bias_bit must be 2..32 (got %d / %d)",
+                                 what, i, l->weight_bit, l->bias_bit);
+            if (!l->weight_integer || !l->bias_integer || !l->scale)
+                return mlp_error(DQRM_E_INVALID, "%s: layer %d: null weight_integer / bias_integer / scale", what, i);
+        }
+    }
+    return DQRM_OK;
+}
+
+int check_flags(uint32_t flags, uint32_t known, const char* what) {
+    if (flags & ~known) return mlp_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    return DQRM_OK;
+}
+
+// an array of L device pointers, none null
+int check_ptrs(const void* const* p, int L, const char* name, const char* what) {
+    if (!p) return mlp_error(DQRM_E_INVALID, "%s: null %s array", what, name);
+    for (int i = 0; i < L; ++i)
+        if (!p[i]) return mlp_error(DQRM_E_INVALID, "%s: null %s[%d]", what, name, i);
+    return DQRM_OK;
+}
+
+// widest tensor between two layers (0 for a stack of one layer)
+int64_t max_hidden(const dqrm_mlp* m) {
+    int64_t w = 0;
+    for (int i = 0; i + 1 < m->num_layers; ++i) w = m->layers[i].out_features > w ? m->layers[i].out_features : w;
+    return w;
+}
+
+bool has_tensor_layer(const dqrm_mlp* m) {
+    for (int i = 0; i < m->num_layers; ++i)
+        if (m->quantized[i] && !m->layers[i].per_channel) return true;
+    return false;
+}
+
+int64_t total_rows(const dqrm_mlp* m) {
+    int64_t r = 0;
+    for (int i = 0; i < m->num_layers; ++i) r += m->layers[i].out_features;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dqrm_mlp_fwd(const dqrm_mlp* m, uint32_t flags, const float* x, int64_t B, float* const* y, void* stream) {
+    const char* what = "dqrm_mlp_fwd";
+    int rc = check_stack(m, what);
+    if (rc) return rc;
+    if ((rc = check_flags(flags, DQRM_MLP_FRESH, what))) return rc;
+    if (B < 0 || B > INT32_MAX) return mlp_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!y) return mlp_error(DQRM_E_INVALID, "%s: null y array", what);
+    if (B == 0) return DQRM_OK;
+    if (!x) return mlp_error(DQRM_E_INVALID, "%s: null x", what);
+    if ((rc = check_ptrs((const void* const*)y, m->num_layers, "y", what))) return rc;
+    for (int i = 0; i < m->num_layers; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        if (m->quantized[i] && !(flags & DQRM_MLP_FRESH) && (rc = dqrm_linear_wquant(l, stream))) return rc;
+        if ((rc = dqrm_linear_fwd_act(l, m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, B, y[i], stream)))
+            return rc;
+    }
+    return DQRM_OK;
+}
+
+size_t dqrm_mlp_bwd_scratch_bytes(const dqrm_mlp* m, int64_t B) {
+    if (check_stack(m, "dqrm_mlp_bwd_scratch_bytes") || B < 0 || B > INT32_MAX) return 0;
+    return (size_t)2 * (size_t)B * (size_t)max_hidden(m) * sizeof(float);
+}
+
+int dqrm_mlp_bwd(const dqrm_mlp* m, const float* x, const float* const* y, const float* dy, int64_t B, float* dx,
+                 float* const* dw, float* const* db, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* what = "dqrm_mlp_bwd";
+    int rc = check_stack(m, what);
+    if (rc) return rc;
+    if (B < 1 || B > INT32_MAX) return mlp_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!x || !dy) return mlp_error(DQRM_E_INVALID, "%s: null x / dy", what);
+    const int L = m->num_layers;
+    if ((rc = check_ptrs((const void* const*)y, L, "y", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
+    const size_t half = (size_t)B * (size_t)max_hidden(m) * sizeof(float);
+    if (half && (!scratch || scratch_bytes < 2 * half))
+        return mlp_error(DQRM_E_INVALID, "%s: scratch of %zu bytes, dqrm_mlp_bwd_scratch_bytes asks for %zu", what,
+                         scratch ? scratch_bytes : (size_t)0, 2 * half);
+    float* buf[2] = {(float*)scratch, (float*)((char*)scratch + half)};
+    for (int i = L - 1; i >= 0; --i) {
+        // layer i's dx is layer i-1's dy: buf[i & 1] is written while buf[(i + 1) & 1] is read
+        const float* dyi = i == L - 1 ? dy : buf[(i + 1) & 1];
+        float* dxi = i == 0 ? dx : buf[i & 1];
+        if ((rc = dqrm_linear_bwd_act(&m->layers[i], m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, y[i], dyi, B,
+                                      dxi, dw[i], db[i], stream)))
+            return rc;
+    }
+    return DQRM_OK;
+}
+
+size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* m) {
+    if (check_stack(m, "dqrm_mlp_sgd_workspace_bytes") || !has_tensor_layer(m)) return 0;
+    return (size_t)total_rows(m) * sizeof(float);
+}
+
+int dqrm_mlp_sgd(const dqrm_mlp* m, uint32_t flags, const float* const* dw, const float* const* db,
+                 const float* const* gscale, float lr, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "dqrm_mlp_sgd";
+    int rc = check_stack(m, what);
+    if (rc) return rc;
+    if ((rc = check_flags(flags, DQRM_MLP_REQUANT, what))) return rc;
+    const int L = m->num_layers;
+    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
+    if (gscale && (rc = check_ptrs((const void* const*)gscale, L, "gscale", what))) return rc;
+    const int64_t rows = total_rows(m);
+    if (rows > INT32_MAX) return mlp_error(DQRM_E_CAPACITY, "%s: %lld weight rows exceed the grid's index range", what,
+                                           (long long)rows);
+    const bool requant = (flags & DQRM_MLP_REQUANT) != 0;
+    const bool two = requant && has_tensor_layer(m);
+    if (two && (!workspace || workspace_bytes < (size_t)rows * sizeof(float)))
+        return mlp_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, dqrm_mlp_sgd_workspace_bytes asks for %zu", what,
+                         workspace ? workspace_bytes : (size_t)0, (size_t)rows * sizeof(float));
+    SgdArgs a{};
+    int row0 = 0;
+    for (int i = 0; i < L; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        SgdLayer& d = a.layer[i];
+        d.W = const_cast<float*>(l->weight);
+        d.b = const_cast<float*>(l->bias);
+        d.dw = dw[i];
+        d.db = db[i];
+        d.gs = gscale ? gscale[i] : nullptr;
+        d.out = l->out_features;
+        d.in = l->in_features;
+        d.row0 = row0;
+        row0 += l->out_features;
+        d.mode = UPDATE_ONLY;
+        if (requant && m->quantized[i]) {
+            const int64_t nw = ((int64_t)1 << (l->weight_bit - 1)) - 1, nb = ((int64_t)1 << (l->bias_bit - 1)) - 1;
+            d.wi = l->weight_integer;
+            d.bi = l->bias_integer;
+            d.scale = l->scale;
+            d.n = (float)nw;
+            d.wlo = (float)(-nw - 1);
+            d.whi = (float)nw;
+            d.blo = (float)(-nb - 1);
+            d.bhi = (float)nb;
+            d.mode = l->per_channel ? REQUANT_ROWS : REQUANT_TENSOR;
+        }
+    }
+    a.num_layers = L;
+    a.total_rows = (int)rows;
+    a.nlr = -lr;
+    a.rowmax = two ? (float*)workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((rows + SRPW - 1) / SRPW));
+    hipLaunchKernelGGL(k_mlp_sgd, grid, dim3(SWG), 0, st, a);
+    MHIP_TRY(hipGetLastError());
+    if (two) {
+        hipLaunchKernelGGL(k_mlp_requant_tensor, grid, dim3(SWG), 0, st, a);
+        MHIP_TRY(hipGetLastError());
+    }
+    return DQRM_OK;
+}
+
+}  // extern "C"

@@ -29,6 +29,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _lib as L
+from .linear import note_raw_write
 from .tables import _ptr, _stream_handle
 
 _WIRE_DTYPE = {L.DQRM_WIRE_F16: torch.float16, L.DQRM_WIRE_I32: torch.int32, L.DQRM_WIRE_F32: torch.float32}
@@ -149,6 +150,7 @@ class HipDenseKernels:
                 "dqrm_dense_grad_decode")
 
     def update(self, s, lr):
+        note_raw_write()  # the parameters change behind torch's version counters
         L.check(self.lib.dqrm_dense_update(C.byref(self._c), _ptr(s), float(lr), _stream_handle()),
                 "dqrm_dense_update")
 

@@ -51,6 +51,21 @@ from .tables import _stream_handle
 
 _ACTS = {None: L.DQRM_ACT_NONE, "relu": L.DQRM_ACT_RELU, "sigmoid": L.DQRM_ACT_SIGMOID}
 
+# Counts the package's writes to a QuantLinear weight or bias through a raw pointer (a kernel
+# handed ``data_ptr()``): torch's version counters do not see those, so mlp.MLPStack compares this
+# epoch as well before it trusts the integers a layer holds.
+_raw_write_epoch = 0
+
+
+def note_raw_write() -> None:
+    """Called by every place in the package that lets a kernel write a dense parameter in place."""
+    global _raw_write_epoch
+    _raw_write_epoch += 1
+
+
+def raw_write_epoch() -> int:
+    return _raw_write_epoch
+
 
 def _check_input(x: torch.Tensor, layer: "QuantLinear") -> None:
     w = layer.weight

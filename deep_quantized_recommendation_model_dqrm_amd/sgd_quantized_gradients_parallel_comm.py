@@ -37,6 +37,7 @@ from torch import nn
 from . import _lib as L
 from .comm import ConsolidatedExchange, MultiSetExchange, SparseGradExchange
 from .dense import DenseGradExchange
+from .linear import note_raw_write
 from .quant_modules_not_quantize_grad import (_QuantEmbeddingBase, can_consolidate, consolidate_tables,
                                               error_check_due, poll_device_errors, set_error_check_interval)
 
@@ -435,6 +436,7 @@ def _sync_params(params, num_gpus: int, group, table_of: dict) -> set:
             changed.add(param.data_ptr())
         elif not _ring_mean_is_identity(param, world, num_gpus, absmax[i]):
             if param.dtype == torch.float32 and param.is_contiguous() and param.data_ptr() % 16 == 0:
+                note_raw_write()  # a dense parameter may change behind torch's version counter
                 L.check(lib.dqrm_replica_mean(param.data_ptr(), param.numel(), world, inv, _stream()),
                         "dqrm_replica_mean")
             else:  # same arithmetic in torch (element-wise, IEEE-rounded)

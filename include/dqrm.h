@@ -80,7 +80,10 @@ extern "C" {
                                   dqrm_linear_wquant_qact, dqrm_linear_fwd_qact,
                                   dqrm_linear_bwd_qact;
                                   likewise within 12: the loss head, dqrm_loss (DLRMLoss),
-                                  DQRM_LOSS_*: dqrm_loss_fwd, dqrm_loss_bwd */
+                                  DQRM_LOSS_*: dqrm_loss_fwd, dqrm_loss_bwd;
+                                  likewise within 12: a whole MLP stack per call, dqrm_mlp
+                                  (MLPStack): dqrm_mlp_fwd, dqrm_mlp_bwd_scratch_bytes,
+                                  dqrm_mlp_bwd, dqrm_mlp_sgd_workspace_bytes, dqrm_mlp_sgd */
 
 /* status codes */
 #define DQRM_OK            0
@@ -693,6 +696,64 @@ int dqrm_linear_fwd_qact(const dqrm_linear* layer, int act, const float* x, cons
 int dqrm_linear_bwd_qact(const dqrm_linear* layer, int act, const float* x, const float* y, const float* dy,
                          const float* prev, const float* out_scale, int64_t B,
                          float* dx, float* dw, float* db, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * A whole MLP stack (create_mlp's QuantLinear layers with their fused activations) per host
+ * call, csrc/dqrm_mlp.hip. The struct and its three arrays are HOST memory; the pointers inside
+ * each dqrm_linear, and the entries of every pointer array below, are device pointers.
+ * Weight-only layers: there is no integer-activation (quantize_activation) form.
+ * ------------------------------------------------------------------------------ */
+#define DQRM_MLP_MAX_LAYERS 16   /* the update kernel takes the layer descriptors by value */
+typedef struct dqrm_mlp {
+    int32_t num_layers;           /* L, 1..DQRM_MLP_MAX_LAYERS */
+    int32_t reserved;
+    const dqrm_linear* layers;    /* HOST [L]; layers[i].in_features == layers[i-1].out_features */
+    const int32_t* quantized;     /* HOST [L]: 0 = full_precision_flag */
+    const int32_t* act;           /* HOST [L]: DQRM_ACT_* fused into layer i */
+} dqrm_mlp;
+
+#define DQRM_MLP_FRESH   1u   /* fwd: integers and scales are current, launch no wquant */
+#define DQRM_MLP_REQUANT 1u   /* sgd: refresh scale / weight_integer / bias_integer of quantized layers */
+
+/* The stack's forward: for layer i = 0..L-1, dqrm_linear_wquant (quantized layers, unless
+ * DQRM_MLP_FRESH) and dqrm_linear_fwd_act with x_i = x or y[i-1], by calling those exports, in
+ * that order: the per-layer calls' launches and bits. y is a HOST array of L device pointers,
+ * y[i] is [B][out_i]; every y[i] is also what the backward reads. L launches, plus the wquant
+ * launches when not fresh. B == 0: DQRM_OK, no launch. */
+int dqrm_mlp_fwd(const dqrm_mlp* stack, uint32_t flags, const float* x, int64_t B, float* const* y, void* stream);
+
+/* The stack's backward: dqrm_linear_bwd_act from layer L-1 to layer 0; layer i's dx is written to
+ * one of two scratch buffers of [B][max hidden width] floats and is layer i-1's dy; layer 0's goes
+ * to dx (NULL: skipped). dw / db are HOST arrays of L device pointers. The scratch is
+ * dqrm_mlp_bwd_scratch_bytes = 2 * B * (max over i < L-1 of out_i) * 4 bytes (0 for one layer).
+ * 2L - 1 launches, 2L with dx. */
+size_t dqrm_mlp_bwd_scratch_bytes(const dqrm_mlp* stack, int64_t B);
+int dqrm_mlp_bwd(const dqrm_mlp* stack, const float* x, const float* const* y, const float* dy, int64_t B,
+                 float* dx, float* const* dw, float* const* db, void* scratch, size_t scratch_bytes, void* stream);
+
+/* SGD on every layer of the stack, and (DQRM_MLP_REQUANT) the quantization the next forward
+ * needs, so that it can run DQRM_MLP_FRESH. weight / bias of the layers are WRITTEN (the struct's
+ * const is dqrm_linear's). Every product and sum is one separately rounded f32 operation:
+ *   nlr = -lr
+ *   W[o,k] = W[o,k] + (nlr * dw[o,k])                      gscale == NULL  (s_q_g_p_c.py:645-646)
+ *   W[o,k] = W[o,k] + ((nlr * dw[o,k]) * gscale[l][o])     gscale given    (:642-643, dqrm_dense_update)
+ *   b[o]   = b[o]   + (nlr * db[o])  [ * gscale[l][out_l] ]
+ * gscale: HOST array of L device pointers, gscale[l] is [out_l + 1]: the rows' scales, then the
+ * bias's. With DQRM_MLP_REQUANT a quantized layer's scale, weight_integer and bias_integer
+ * afterwards hold exactly what dqrm_linear_wquant writes from the updated W and b; full-precision
+ * layers are updated only. One launch; two when DQRM_MLP_REQUANT meets a quantized layer without
+ * per_channel, whose row maxima pass through the workspace (dqrm_mlp_sgd_workspace_bytes: 4 bytes
+ * per weight row of the stack, 0 when no quantized layer is per tensor). No atomics, no memset,
+ * nothing that depends on workgroups being resident together.
+ *
+ * All five calls: DQRM_E_INVALID before any launch for a null stack or array, num_layers outside
+ * 1..DQRM_MLP_MAX_LAYERS, a width chain that does not match, act outside 0..2, what
+ * dqrm_linear_wquant / _fwd / _bwd reject in a layer, unknown flags, a null x / dy or entry of
+ * y / dw / db / gscale, a short scratch or workspace, B < 0 (B < 1 in the backward). The two size
+ * queries return 0 for a stack they reject. */
+size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* stack);
+int dqrm_mlp_sgd(const dqrm_mlp* stack, uint32_t flags, const float* const* dw, const float* const* db,
+                 const float* const* gscale, float lr, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * QuantAct: fake-quantized activations with a running range (quantization_supp/
