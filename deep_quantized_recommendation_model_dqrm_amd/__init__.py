@@ -12,6 +12,8 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
   * ``DLRM_Net.forward``'s clamp and ``loss_fn_wrap``            (``DLRMLoss``: BCE / MSE / weighted BCE with
                                                                 its gradient in one launch, a mean whose
                                                                 bits depend on the batch size alone)
+  * ``DLRM_Net`` itself and one iteration of its training loop  (``DQRMNet``: the stages above as one
+                                                                model, ``train_step`` one host call)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
@@ -30,6 +32,7 @@ from .act import QuantAct
 from .mlp import FusedActivation, MLPStack, apply_mlp, create_mlp, fuse_activations, unfuse_activations
 from .interaction import DotInteraction, interact_features
 from .loss import DLRMLoss, loss_fn_wrap
+from .model import DQRMNet
 from . import quantized_ops
 
 __all__ = [
@@ -60,6 +63,7 @@ __all__ = [
     "interact_features",
     "DLRMLoss",
     "loss_fn_wrap",
+    "DQRMNet",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

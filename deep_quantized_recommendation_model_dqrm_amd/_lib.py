@@ -64,6 +64,11 @@ DQRM_MLP_MAX_LAYERS = 16
 DQRM_MLP_FRESH = 1
 DQRM_MLP_REQUANT = 1
 
+DQRM_MODEL_MLP_FRESH = 1
+DQRM_MODEL_REQUANT = 2
+DQRM_MODEL_NO_UPDATE = 4
+DQRM_MODEL_EMB_READY = 8
+
 DQRM_LOSS_BCE = 0
 DQRM_LOSS_MSE = 1
 DQRM_LOSS_WBCE = 2
@@ -121,6 +126,13 @@ EXPORTED_SYMBOLS = (
     "dqrm_mlp_bwd",
     "dqrm_mlp_sgd_workspace_bytes",
     "dqrm_mlp_sgd",
+    "dqrm_mlp_sgd_multi_workspace_bytes",
+    "dqrm_mlp_sgd_multi",
+    "dqrm_model_workspace_bytes",
+    "dqrm_model_workspace_layout",
+    "dqrm_model_fwd",
+    "dqrm_model_step",
+    "dqrm_model_step_launches",
     "dqrm_act_quant_workspace_bytes",
     "dqrm_act_quant_fwd",
     "dqrm_act_quant_bwd",
@@ -285,6 +297,28 @@ class Interact(C.Structure):
     ]
 
 
+class Model(C.Structure):
+    """Mirror of ``dqrm_model`` (include/dqrm.h): host pointers to the stages' structs."""
+
+    _fields_ = [
+        ("tables", C.POINTER(TableSet)),
+        ("bottom", C.POINTER(MLP)),
+        ("top", C.POINTER(MLP)),
+        ("loss", C.POINTER(Loss)),
+        ("interact", Interact),
+        ("embedding_bit", C.c_int32),
+        ("emb_fwd_flags", C.c_uint32),
+        ("ste", C.c_int32),
+        ("repack_bits", C.c_int32),
+    ]
+
+
+class ModelLayout(C.Structure):
+    """Mirror of ``dqrm_model_layout`` (include/dqrm.h): byte offsets into the workspace."""
+
+    _fields_ = [(name, C.c_size_t) for name in ("slab", "r", "p", "dr", "dx", "demb", "total")]
+
+
 class Exchange(C.Structure):
     """Mirror of ``dqrm_exchange`` (include/dqrm.h): one rank's exchange buffers."""
 
@@ -342,6 +376,8 @@ def load(path: str | None = None) -> C.CDLL:
     AQ = C.POINTER(ActQuant)
     ML = C.POINTER(MLP)
     PP = C.POINTER(C.c_void_p)  # a host array of device pointers
+    MO = C.POINTER(Model)
+    MS = C.POINTER(ML)  # a host array of stacks
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -438,6 +474,13 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_mlp_bwd": (C.c_int, [ML, P, PP, P, C.c_int64, P, PP, PP, P, C.c_size_t, P]),
         "dqrm_mlp_sgd_workspace_bytes": (C.c_size_t, [ML]),
         "dqrm_mlp_sgd": (C.c_int, [ML, C.c_uint32, PP, PP, PP, C.c_float, P, C.c_size_t, P]),
+        "dqrm_mlp_sgd_multi_workspace_bytes": (C.c_size_t, [MS, C.c_int]),
+        "dqrm_mlp_sgd_multi": (C.c_int, [MS, C.c_int, C.c_uint32, PP, PP, PP, C.c_float, P, C.c_size_t, P]),
+        "dqrm_model_workspace_bytes": (C.c_size_t, [MO, C.c_int64, C.c_int64]),
+        "dqrm_model_workspace_layout": (C.c_int, [MO, C.c_int64, C.c_int64, C.POINTER(ModelLayout)]),
+        "dqrm_model_fwd": (C.c_int, [MO, BA, C.c_uint32, P, P, P, P, P, C.c_size_t, P]),
+        "dqrm_model_step": (C.c_int, [MO, BA, BA, C.c_uint32, P, P, C.c_float, P, P, P, PP, PP, P, C.c_size_t, P]),
+        "dqrm_model_step_launches": (C.c_int, [MO, BA, BA, C.c_uint32]),
         "dqrm_act_quant_workspace_bytes": (C.c_int64, [C.c_int64]),
         "dqrm_act_quant_fwd": (C.c_int, [AQ, P, C.c_int64, P, P, P]),
         "dqrm_act_quant_bwd": (C.c_int, [P, P, C.c_int64, P, P]),

@@ -5272,6 +5272,45 @@ int dqrm_bwd_sgd_fwd_is_one_launch(const dqrm_table_set* set, const dqrm_batch* 
     return sgd_small_plan(set, batch, next, fwd_flags, nullptr) == 2 ? 1 : 0;
 }
 
+// The whole-model step (dqrm_model.hip) validates its embedding stage before its first launch:
+// everything dqrm_emb_fwd and dqrm_emb_bwd_sgd / _sgd_fwd reject, apart from the out / dy pointers
+// and strides, which that caller lays out itself. batch == NULL: the set alone. training == 0:
+// the forward's checks only. next: the batch whose forward follows the update (nullable).
+__attribute__((visibility("hidden"))) int dqrm_internal_emb_check(const dqrm_table_set* set, const dqrm_batch* batch,
+                                                                  const dqrm_batch* next, int bits, uint32_t fwd_flags,
+                                                                  int repack_bits, int training, const char* who) {
+    int rc = check_set(set);
+    if (rc) return rc;
+    if (!(fwd_flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
+        return set_error(DQRM_E_INVALID, "%s: embedding_bit %d unsupported", who, bits);
+    if ((fwd_flags & DQRM_FWD_USE_PACKED) && (!set->packed || bits != 4))
+        return set_error(DQRM_E_INVALID, "%s: packed path needs packed rows and bits == 4", who);
+    if (repack_bits && (repack_bits != 4 || !set->packed))
+        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", who, repack_bits);
+    if (!batch) return DQRM_OK;
+    if ((rc = check_batch(batch, who))) return rc;
+    if (next && (rc = check_batch(next, who))) return rc;
+    if (!training) return DQRM_OK;
+    if (bwd_lookup_cap(batch) > 0x3fffffffll)
+        return set_error(DQRM_E_CAPACITY, "%s: max_lookups %lld too large", who, (long long)bwd_lookup_cap(batch));
+    if (set->total_rows > 0xffffffffll) return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 rows", who);
+    return DQRM_OK;
+}
+
+// launches of dqrm_emb_bwd_sgd (next == NULL) / dqrm_emb_bwd_sgd_fwd on arguments that passed
+// dqrm_internal_emb_check
+__attribute__((visibility("hidden"))) int dqrm_internal_emb_bwd_sgd_launches(const dqrm_table_set* set,
+                                                                             const dqrm_batch* batch,
+                                                                             const dqrm_batch* next,
+                                                                             uint32_t fwd_flags) {
+    const int fwd = next && next->num_bags > 0 ? 1 : 0;
+    if (batch->num_bags <= 0) return fwd;
+    const int plan = sgd_small_plan(set, batch, next, fwd_flags, nullptr);
+    if (plan == 2) return 1;
+    if (plan == 1) return 1 + fwd;
+    return 1 + finalize_launch() + fwd;
+}
+
 static int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
                            int64_t dy_stride_b, int ste, const int64_t* ws_cap_base, int64_t ws_cap_total,
                            int32_t* ws_rows, float* ws_vals, int32_t* ws_ucount, float* ws_absmax, int grad_bits,

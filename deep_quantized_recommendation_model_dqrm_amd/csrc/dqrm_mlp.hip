@@ -19,7 +19,8 @@
 // layer needs the maximum over all its rows: launch 1 leaves every row's max|W| in the workspace,
 // launch 2 has every wave of the layer reduce those row maxima itself (a maximum does not depend
 // on the order it is taken in) and write its row's integers. No atomics, no memset, no workgroup
-// waits on another.
+// waits on another. dqrm_mlp_sgd_multi is the same two kernels over the rows of several stacks'
+// layers (a model's bottom and top MLP): one descriptor list, one grid, one launch.
 //
 // Compiled with -ffp-contract=off: `nlr * dw`, `* gscale` and `W + ...` are separately rounded.
 
@@ -233,6 +234,61 @@ int64_t total_rows(const dqrm_mlp* m) {
     return r;
 }
 
+// one layer's descriptor of the update grid; requant: refresh its integers and scale too
+void fill_layer(SgdLayer& d, const dqrm_linear* l, bool requant, const float* dw, const float* db, const float* gs,
+                int row0) {
+    d.W = const_cast<float*>(l->weight);
+    d.b = const_cast<float*>(l->bias);
+    d.dw = dw;
+    d.db = db;
+    d.gs = gs;
+    d.out = l->out_features;
+    d.in = l->in_features;
+    d.row0 = row0;
+    d.mode = UPDATE_ONLY;
+    if (requant) {
+        const int64_t nw = ((int64_t)1 << (l->weight_bit - 1)) - 1, nb = ((int64_t)1 << (l->bias_bit - 1)) - 1;
+        d.wi = l->weight_integer;
+        d.bi = l->bias_integer;
+        d.scale = l->scale;
+        d.n = (float)nw;
+        d.wlo = (float)(-nw - 1);
+        d.whi = (float)nw;
+        d.blo = (float)(-nb - 1);
+        d.bhi = (float)nb;
+        d.mode = l->per_channel ? REQUANT_ROWS : REQUANT_TENSOR;
+    }
+}
+
+// the update's launch, and the per-tensor layers' second one
+int launch_sgd(const SgdArgs& a, bool two, hipStream_t st) {
+    const dim3 grid((unsigned)((a.total_rows + SRPW - 1) / SRPW));
+    hipLaunchKernelGGL(k_mlp_sgd, grid, dim3(SWG), 0, st, a);
+    MHIP_TRY(hipGetLastError());
+    if (two) {
+        hipLaunchKernelGGL(k_mlp_requant_tensor, grid, dim3(SWG), 0, st, a);
+        MHIP_TRY(hipGetLastError());
+    }
+    return DQRM_OK;
+}
+
+// several stacks for one update launch: each a valid stack, DQRM_MLP_MAX_LAYERS layers in all
+int check_stacks(const dqrm_mlp* const* stacks, int num_stacks, const char* what) {
+    if (!stacks) return mlp_error(DQRM_E_INVALID, "%s: null stacks array", what);
+    if (num_stacks < 1 || num_stacks > DQRM_MLP_MAX_LAYERS)
+        return mlp_error(DQRM_E_INVALID, "%s: num_stacks must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS, num_stacks);
+    int L = 0;
+    for (int s = 0; s < num_stacks; ++s) {
+        int rc = check_stack(stacks[s], what);
+        if (rc) return rc;
+        L += stacks[s]->num_layers;
+    }
+    if (L > DQRM_MLP_MAX_LAYERS)
+        return mlp_error(DQRM_E_INVALID, "%s: the stacks have %d layers in all, at most %d fit one launch", what, L,
+                         DQRM_MLP_MAX_LAYERS);
+    return DQRM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -312,46 +368,72 @@ int dqrm_mlp_sgd(const dqrm_mlp* m, uint32_t flags, const float* const* dw, cons
         return mlp_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, dqrm_mlp_sgd_workspace_bytes asks for %zu", what,
                          workspace ? workspace_bytes : (size_t)0, (size_t)rows * sizeof(float));
     SgdArgs a{};
-    int row0 = 0;
-    for (int i = 0; i < L; ++i) {
-        const dqrm_linear* l = &m->layers[i];
-        SgdLayer& d = a.layer[i];
-        d.W = const_cast<float*>(l->weight);
-        d.b = const_cast<float*>(l->bias);
-        d.dw = dw[i];
-        d.db = db[i];
-        d.gs = gscale ? gscale[i] : nullptr;
-        d.out = l->out_features;
-        d.in = l->in_features;
-        d.row0 = row0;
-        row0 += l->out_features;
-        d.mode = UPDATE_ONLY;
-        if (requant && m->quantized[i]) {
-            const int64_t nw = ((int64_t)1 << (l->weight_bit - 1)) - 1, nb = ((int64_t)1 << (l->bias_bit - 1)) - 1;
-            d.wi = l->weight_integer;
-            d.bi = l->bias_integer;
-            d.scale = l->scale;
-            d.n = (float)nw;
-            d.wlo = (float)(-nw - 1);
-            d.whi = (float)nw;
-            d.blo = (float)(-nb - 1);
-            d.bhi = (float)nb;
-            d.mode = l->per_channel ? REQUANT_ROWS : REQUANT_TENSOR;
-        }
+    for (int i = 0, row0 = 0; i < L; row0 += m->layers[i].out_features, ++i)
+        fill_layer(a.layer[i], &m->layers[i], requant && m->quantized[i], dw[i], db[i], gscale ? gscale[i] : nullptr,
+                   row0);
+    a.num_layers = L;
+    a.total_rows = (int)rows;
+    a.nlr = -lr;
+    a.rowmax = two ? (float*)workspace : nullptr;
+    return launch_sgd(a, two, (hipStream_t)stream);
+}
+
+size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num_stacks) {
+    const char* what = "dqrm_mlp_sgd_multi_workspace_bytes";
+    if (check_stacks(stacks, num_stacks, what)) return 0;
+    int64_t rows = 0;
+    bool tensor = false;
+    for (int s = 0; s < num_stacks; ++s) {
+        rows += total_rows(stacks[s]);
+        tensor = tensor || has_tensor_layer(stacks[s]);
+    }
+    return tensor ? (size_t)rows * sizeof(float) : 0;
+}
+
+int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
+                       const float* const* db, const float* const* gscale, float lr, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    const char* what = "dqrm_mlp_sgd_multi";
+    int rc = check_stacks(stacks, num_stacks, what);
+    if (rc) return rc;
+    if ((rc = check_flags(flags, DQRM_MLP_REQUANT, what))) return rc;
+    int L = 0;
+    int64_t rows = 0;
+    bool tensor = false;
+    for (int s = 0; s < num_stacks; ++s) {
+        L += stacks[s]->num_layers;
+        rows += total_rows(stacks[s]);
+        tensor = tensor || has_tensor_layer(stacks[s]);
+    }
+    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
+    if (gscale && (rc = check_ptrs((const void* const*)gscale, L, "gscale", what))) return rc;
+    if (rows > INT32_MAX) return mlp_error(DQRM_E_CAPACITY, "%s: %lld weight rows exceed the grid's index range", what,
+                                           (long long)rows);
+    const bool requant = (flags & DQRM_MLP_REQUANT) != 0;
+    const bool two = requant && tensor;
+    if (two && (!workspace || workspace_bytes < (size_t)rows * sizeof(float)))
+        return mlp_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, dqrm_mlp_sgd_multi_workspace_bytes asks for %zu",
+                         what, workspace ? workspace_bytes : (size_t)0, (size_t)rows * sizeof(float));
+    // the stacks' layers back to back: one descriptor list, one grid over all their rows
+    SgdArgs a{};
+    int k = 0, row0 = 0;
+    for (int s = 0; s < num_stacks; ++s) {
+        const dqrm_mlp* m = stacks[s];
+        for (int i = 0; i < m->num_layers; row0 += m->layers[i].out_features, ++i, ++k)
+            fill_layer(a.layer[k], &m->layers[i], requant && m->quantized[i], dw[k], db[k],
+                       gscale ? gscale[k] : nullptr, row0);
     }
     a.num_layers = L;
     a.total_rows = (int)rows;
     a.nlr = -lr;
     a.rowmax = two ? (float*)workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((rows + SRPW - 1) / SRPW));
-    hipLaunchKernelGGL(k_mlp_sgd, grid, dim3(SWG), 0, st, a);
-    MHIP_TRY(hipGetLastError());
-    if (two) {
-        hipLaunchKernelGGL(k_mlp_requant_tensor, grid, dim3(SWG), 0, st, a);
-        MHIP_TRY(hipGetLastError());
-    }
-    return DQRM_OK;
+    return launch_sgd(a, two, (hipStream_t)stream);
+}
+
+// dqrm_model.hip validates its stacks before its first launch
+__attribute__((visibility("hidden"))) int dqrm_internal_check_mlp(const dqrm_mlp* m, const char* what) {
+    return check_stack(m, what);
 }
 
 }  // extern "C"

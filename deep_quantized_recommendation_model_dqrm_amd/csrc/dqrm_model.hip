@@ -1,0 +1,317 @@
+// dqrm_model.hip — the whole DLRM per host call: dqrm_model_fwd (inference) and dqrm_model_step
+// (one training step at world size 1), gfx950.
+//
+// Reference (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM @ 2024-10-24): DLRM_Net.forward /
+// sequential_forward (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:805-880: apply_mlp(bot_l),
+// apply_emb, interact_features, apply_mlp(top_l), the clamp) and one iteration of the training loop
+// (loss_fn_wrap, E.backward(), the optimizer's step).
+//
+// There is no kernel in this file and no arithmetic: both calls validate everything first, cut the
+// caller's workspace, and then call the stage exports (dqrm_emb_fwd, dqrm_mlp_fwd, dqrm_interact_*,
+// dqrm_loss_fwd, dqrm_mlp_bwd, dqrm_emb_bwd_sgd[_fwd], dqrm_mlp_sgd_multi) in the order a
+// stage-by-stage caller would, on the same stream. Their bits are those calls' bits by
+// construction. What is saved is the host's work between the stages: one ABI crossing per step
+// instead of a dozen, no autograd graph, no per-stage tensor allocation.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdarg.h>
+
+#include "../../include/dqrm.h"
+
+extern "C" int dqrm_internal_set_error(int code, const char* msg);            // dqrm_kernels.hip (hidden)
+extern "C" int dqrm_internal_check_mlp(const dqrm_mlp* m, const char* what);  // dqrm_mlp.hip (hidden)
+extern "C" int dqrm_internal_emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
+                                       int bits, uint32_t fwd_flags, int repack_bits, int training,
+                                       const char* who);                      // dqrm_kernels.hip (hidden)
+extern "C" int dqrm_internal_emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch,
+                                                  const dqrm_batch* next, uint32_t fwd_flags);
+
+namespace {
+
+constexpr int64_t kMaxB = (int64_t)1 << 20;  // dqrm_loss_fwd's one workgroup
+constexpr uint32_t kStepFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_REQUANT | DQRM_MODEL_NO_UPDATE | DQRM_MODEL_EMB_READY;
+constexpr uint32_t kFwdFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_EMB_READY;
+
+int model_error(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return dqrm_internal_set_error(code, buf);
+}
+
+// the struct alone: members, every stage's own rules, and the widths between the stages
+int check_model(const dqrm_model* m, const char* what) {
+    if (!m) return model_error(DQRM_E_INVALID, "%s: null model", what);
+    if (!m->tables || !m->bottom || !m->top || !m->loss)
+        return model_error(DQRM_E_INVALID, "%s: null tables / bottom / top / loss", what);
+    int rc = dqrm_internal_emb_check(m->tables, nullptr, nullptr, m->embedding_bit, m->emb_fwd_flags, m->repack_bits, 0,
+                                     what);
+    if (rc) return rc;
+    if ((rc = dqrm_internal_check_mlp(m->bottom, what))) return rc;
+    if ((rc = dqrm_internal_check_mlp(m->top, what))) return rc;
+    const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
+    if (Lb + Lt > DQRM_MLP_MAX_LAYERS)
+        return model_error(DQRM_E_INVALID, "%s: bottom and top have %d layers in all, at most %d fit the update's launch",
+                           what, Lb + Lt, DQRM_MLP_MAX_LAYERS);
+    const int T = m->tables->num_tables, D = m->tables->dim;
+    const dqrm_interact* ic = &m->interact;
+    if (ic->num_features != T + 1 || ic->dim != D)
+        return model_error(DQRM_E_INVALID, "%s: interact needs num_features = tables + 1 = %d and dim = %d (got %d / %d)",
+                           what, T + 1, D, ic->num_features, ic->dim);
+    if (ic->quant_bits != 0 && (ic->quant_bits < 2 || ic->quant_bits > 16))
+        return model_error(DQRM_E_INVALID, "%s: interact.quant_bits must be 0 or 2..16 (got %d)", what, ic->quant_bits);
+    const int64_t R = dqrm_interact_out_features(T + 1, D, ic->self_interaction);  // F <= 64, D % 4
+    if (R < 0) return (int)R;
+    const dqrm_loss* lc = m->loss;
+    if (lc->kind != DQRM_LOSS_BCE && lc->kind != DQRM_LOSS_MSE && lc->kind != DQRM_LOSS_WBCE)
+        return model_error(DQRM_E_INVALID, "%s: unknown loss kind %d (DQRM_LOSS_BCE / _MSE / _WBCE)", what, lc->kind);
+    if (lc->kind == DQRM_LOSS_WBCE && (!lc->weights || lc->num_weights < 1))
+        return model_error(DQRM_E_INVALID, "%s: DQRM_LOSS_WBCE needs weights (num_weights >= 1, got %d)", what,
+                           lc->num_weights);
+    if (m->bottom->layers[Lb - 1].out_features != D)
+        return model_error(DQRM_E_INVALID, "%s: the bottom stack returns %d features, the tables' dim is %d", what,
+                           m->bottom->layers[Lb - 1].out_features, D);
+    if (m->top->layers[0].in_features != R)
+        return model_error(DQRM_E_INVALID, "%s: the top stack takes %d features, the interaction returns %lld", what,
+                           m->top->layers[0].in_features, (long long)R);
+    if (m->top->layers[Lt - 1].out_features != 1)
+        return model_error(DQRM_E_INVALID, "%s: the top stack must return 1 feature (got %d)", what,
+                           m->top->layers[Lt - 1].out_features);
+    return DQRM_OK;
+}
+
+int check_B(int64_t B, const char* what) {
+    if (B < 1 || B > kMaxB)
+        return model_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
+    return DQRM_OK;
+}
+
+// the cut of the workspace: byte offsets, every part on a 256-byte boundary
+struct Cut {
+    size_t slab, yb[DQRM_MLP_MAX_LAYERS], r, yt[DQRM_MLP_MAX_LAYERS], dr, dx, demb;
+    size_t scratch, scratch_bytes, sort, sort_bytes, iscale, rowmax, rowmax_bytes, total;
+};
+
+size_t take(size_t& at, size_t bytes) {
+    const size_t off = at;
+    at += (bytes + 255) & ~(size_t)255;
+    return off;
+}
+
+// model checked, B in range, max_lookups >= 0
+void cut_workspace(const dqrm_model* m, int64_t B, int64_t max_lookups, Cut* c) {
+    const size_t T = m->tables->num_tables, D = m->tables->dim, f = sizeof(float), b = (size_t)B;
+    const size_t R = (size_t)m->top->layers[0].in_features;
+    size_t at = 0;
+    c->slab = take(at, b * T * D * f);
+    for (int i = 0; i < m->bottom->num_layers; ++i) c->yb[i] = take(at, b * m->bottom->layers[i].out_features * f);
+    c->r = take(at, b * R * f);
+    for (int i = 0; i < m->top->num_layers; ++i) c->yt[i] = take(at, b * m->top->layers[i].out_features * f);
+    c->dr = take(at, b * R * f);
+    c->dx = take(at, b * D * f);
+    c->demb = take(at, b * T * D * f);
+    const size_t sb = dqrm_mlp_bwd_scratch_bytes(m->bottom, B), st = dqrm_mlp_bwd_scratch_bytes(m->top, B);
+    c->scratch_bytes = sb > st ? sb : st;
+    c->scratch = take(at, c->scratch_bytes);
+    c->sort_bytes = dqrm_bwd_workspace_bytes((int)T, max_lookups);
+    c->sort = take(at, c->sort_bytes);
+    c->iscale = take(at, f);
+    const dqrm_mlp* both[2] = {m->bottom, m->top};
+    c->rowmax_bytes = dqrm_mlp_sgd_multi_workspace_bytes(both, 2);
+    c->rowmax = take(at, c->rowmax_bytes);
+    c->total = at;
+}
+
+int check_workspace(const Cut& c, const void* ws, size_t bytes, const char* what) {
+    if (!ws || ((uintptr_t)ws & 15) || bytes < c.total)
+        return model_error(DQRM_E_WORKSPACE, "%s: workspace needs %zu bytes, 16-B aligned (got %zu)", what, c.total,
+                           ws ? bytes : (size_t)0);
+    return DQRM_OK;
+}
+
+// everything about a call but its tensors: the model, the flags, the batches
+int check_call(const dqrm_model* m, const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags, uint32_t known,
+               int training, const char* what) {
+    int rc = check_model(m, what);
+    if (rc) return rc;
+    if (flags & ~known) return model_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    if (!batch) return model_error(DQRM_E_INVALID, "%s: null batch", what);
+    if ((rc = dqrm_internal_emb_check(m->tables, batch, next, m->embedding_bit, m->emb_fwd_flags, m->repack_bits,
+                                      training, what)))
+        return rc;
+    if ((rc = check_B(batch->num_bags, what))) return rc;
+    if (batch->max_lookups < 0) return model_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
+    // the interaction's piece index (dqrm_interact.hip's check_batch)
+    if (batch->num_bags > (int64_t)INT32_MAX / ((int64_t)m->interact.num_features * (m->interact.dim / 4)))
+        return model_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
+                           (long long)batch->num_bags);
+    if (next) {
+        if (flags & DQRM_MODEL_NO_UPDATE)
+            return model_error(DQRM_E_INVALID, "%s: a next batch needs the update (DQRM_MODEL_NO_UPDATE is set)", what);
+        if (next->num_bags != batch->num_bags)
+            return model_error(DQRM_E_INVALID, "%s: next has %lld bags, the slab holds %lld", what,
+                               (long long)next->num_bags, (long long)batch->num_bags);
+    }
+    return DQRM_OK;
+}
+
+int wquant_launches(const dqrm_mlp* s) {
+    int n = 0;
+    for (int i = 0; i < s->num_layers; ++i)
+        if (s->quantized[i]) n += s->layers[i].per_channel ? 1 : 2;
+    return n;
+}
+
+bool has_tensor_layer(const dqrm_mlp* s) {
+    for (int i = 0; i < s->num_layers; ++i)
+        if (s->quantized[i] && !s->layers[i].per_channel) return true;
+    return false;
+}
+
+// the forward both calls share; g == NULL and labels == NULL as dqrm_model_fwd passes them
+int run_forward(const dqrm_model* m, const dqrm_interact* ic, const dqrm_batch* batch, uint32_t flags, const float* x,
+                const float* labels, float* loss, float* z, float* g, char* w, const Cut& c, float* const* yb,
+                float* const* yt, void* stream) {
+    const int64_t B = batch->num_bags, T = m->tables->num_tables, D = m->tables->dim;
+    const uint32_t mf = (flags & DQRM_MODEL_MLP_FRESH) ? DQRM_MLP_FRESH : 0;
+    float* slab = (float*)(w + c.slab);
+    float* r = (float*)(w + c.r);
+    float* iscale = ic->quant_bits ? (float*)(w + c.iscale) : nullptr;
+    int rc;
+    if (!(flags & DQRM_MODEL_EMB_READY) &&
+        (rc = dqrm_emb_fwd(m->tables, batch, m->embedding_bit, m->emb_fwd_flags, slab, D, T * D, stream)))
+        return rc;
+    if ((rc = dqrm_mlp_fwd(m->bottom, mf, x, B, yb, stream))) return rc;
+    const float* xb = yb[m->bottom->num_layers - 1];
+    if (iscale && (rc = dqrm_interact_scale(ic, xb, slab, B, iscale, stream))) return rc;
+    if ((rc = dqrm_interact_fwd(ic, xb, slab, B, iscale, r, stream))) return rc;
+    if ((rc = dqrm_mlp_fwd(m->top, mf, r, B, yt, stream))) return rc;
+    if (!labels) return DQRM_OK;
+    return dqrm_loss_fwd(m->loss, yt[m->top->num_layers - 1], labels, B, loss, g, z, nullptr, stream);
+}
+
+void point_outputs(const dqrm_model* m, char* w, const Cut& c, float** yb, float** yt) {
+    for (int i = 0; i < m->bottom->num_layers; ++i) yb[i] = (float*)(w + c.yb[i]);
+    for (int i = 0; i < m->top->num_layers; ++i) yt[i] = (float*)(w + c.yt[i]);
+}
+
+dqrm_interact slab_interact(const dqrm_model* m) {
+    dqrm_interact ic = m->interact;
+    ic.emb_stride_b = (int64_t)m->tables->num_tables * m->tables->dim;  // the [B][T][D] slab
+    ic.emb_stride_f = m->tables->dim;
+    return ic;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dqrm_model_workspace_layout(const dqrm_model* m, int64_t B, int64_t max_lookups, dqrm_model_layout* out) {
+    const char* what = "dqrm_model_workspace_layout";
+    int rc = check_model(m, what);
+    if (rc) return rc;
+    if ((rc = check_B(B, what))) return rc;
+    if (max_lookups < 0) return model_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
+    if (!out) return model_error(DQRM_E_INVALID, "%s: null out", what);
+    Cut c;
+    cut_workspace(m, B, max_lookups, &c);
+    out->slab = c.slab;
+    out->r = c.r;
+    out->p = c.yt[m->top->num_layers - 1];
+    out->dr = c.dr;
+    out->dx = c.dx;
+    out->demb = c.demb;
+    out->total = c.total;
+    return DQRM_OK;
+}
+
+size_t dqrm_model_workspace_bytes(const dqrm_model* m, int64_t B, int64_t max_lookups) {
+    dqrm_model_layout l;
+    return dqrm_model_workspace_layout(m, B, max_lookups, &l) ? 0 : l.total;
+}
+
+int dqrm_model_fwd(const dqrm_model* m, const dqrm_batch* batch, uint32_t flags, const float* x, const float* labels,
+                   float* loss, float* z, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "dqrm_model_fwd";
+    int rc = check_call(m, batch, nullptr, flags, kFwdFlags, 0, what);
+    if (rc) return rc;
+    if (!x) return model_error(DQRM_E_INVALID, "%s: null x", what);
+    if (labels && !loss) return model_error(DQRM_E_INVALID, "%s: labels need a loss to write (null loss)", what);
+    Cut c;
+    cut_workspace(m, batch->num_bags, batch->max_lookups, &c);
+    if ((rc = check_workspace(c, workspace, workspace_bytes, what))) return rc;
+    char* w = (char*)workspace;
+    float *yb[DQRM_MLP_MAX_LAYERS], *yt[DQRM_MLP_MAX_LAYERS];
+    point_outputs(m, w, c, yb, yt);
+    const dqrm_interact ic = slab_interact(m);
+    return run_forward(m, &ic, batch, flags, x, labels, loss, z, nullptr, w, c, yb, yt, stream);
+}
+
+int dqrm_model_step(const dqrm_model* m, const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags,
+                    const float* x, const float* labels, float lr, float* loss, float* z, float* g, float* const* dw,
+                    float* const* db, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "dqrm_model_step";
+    int rc = check_call(m, batch, next, flags, kStepFlags, 1, what);
+    if (rc) return rc;
+    if (!x || !labels || !loss || !g) return model_error(DQRM_E_INVALID, "%s: null x / labels / loss / g", what);
+    const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
+    if (!dw || !db) return model_error(DQRM_E_INVALID, "%s: null dw / db array", what);
+    for (int i = 0; i < Lb + Lt; ++i)
+        if (!dw[i] || !db[i]) return model_error(DQRM_E_INVALID, "%s: null dw[%d] / db[%d]", what, i, i);
+    Cut c;
+    cut_workspace(m, batch->num_bags, batch->max_lookups, &c);
+    if ((rc = check_workspace(c, workspace, workspace_bytes, what))) return rc;
+    char* w = (char*)workspace;
+    float *yb[DQRM_MLP_MAX_LAYERS], *yt[DQRM_MLP_MAX_LAYERS];
+    point_outputs(m, w, c, yb, yt);
+    const dqrm_interact ic = slab_interact(m);
+    if ((rc = run_forward(m, &ic, batch, flags, x, labels, loss, z, g, w, c, yb, yt, stream))) return rc;
+
+    const int64_t B = batch->num_bags, T = m->tables->num_tables, D = m->tables->dim;
+    float* slab = (float*)(w + c.slab);
+    float* r = (float*)(w + c.r);
+    float* dr = (float*)(w + c.dr);
+    float* dx = (float*)(w + c.dx);
+    float* demb = (float*)(w + c.demb);
+    const float* iscale = ic.quant_bits ? (const float*)(w + c.iscale) : nullptr;
+    void* scratch = c.scratch_bytes ? w + c.scratch : nullptr;
+    // loss.backward() hands the head go = 1.0, and 1.0f * g is g: the top stack's dy is g itself
+    if ((rc = dqrm_mlp_bwd(m->top, r, yt, g, B, dr, dw + Lb, db + Lb, scratch, c.scratch_bytes, stream))) return rc;
+    if ((rc = dqrm_interact_bwd(&ic, yb[Lb - 1], slab, dr, B, iscale, dx, demb, stream))) return rc;
+    if ((rc = dqrm_mlp_bwd(m->bottom, x, yb, dx, B, nullptr, dw, db, scratch, c.scratch_bytes, stream))) return rc;
+    if (flags & DQRM_MODEL_NO_UPDATE) return DQRM_OK;
+
+    void* sort = w + c.sort;
+    if (next)
+        rc = dqrm_emb_bwd_sgd_fwd(m->tables, batch, demb, D, T * D, m->ste, lr, m->repack_bits, sort, c.sort_bytes, next,
+                                  m->embedding_bit, m->emb_fwd_flags, slab, D, T * D, stream);
+    else
+        rc = dqrm_emb_bwd_sgd(m->tables, batch, demb, D, T * D, m->ste, lr, m->repack_bits, sort, c.sort_bytes, stream);
+    if (rc) return rc;
+    const dqrm_mlp* both[2] = {m->bottom, m->top};
+    return dqrm_mlp_sgd_multi(both, 2, (flags & DQRM_MODEL_REQUANT) ? DQRM_MLP_REQUANT : 0, dw, db, nullptr, lr,
+                              c.rowmax_bytes ? w + c.rowmax : nullptr, c.rowmax_bytes, stream);
+}
+
+int dqrm_model_step_launches(const dqrm_model* m, const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags) {
+    const char* what = "dqrm_model_step_launches";
+    int rc = check_call(m, batch, next, flags, kStepFlags, 1, what);
+    if (rc) return rc;
+    const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
+    int n = (flags & DQRM_MODEL_EMB_READY) ? 0 : 1;                     // dqrm_emb_fwd
+    n += Lb + Lt;                                                       // the stacks' forwards
+    if (!(flags & DQRM_MODEL_MLP_FRESH)) n += wquant_launches(m->bottom) + wquant_launches(m->top);
+    n += (m->interact.quant_bits ? 1 : 0) + 1;                          // dqrm_interact_scale, _fwd
+    n += 1;                                                             // dqrm_loss_fwd
+    n += 2 * Lt + 1 + (2 * Lb - 1);                                     // top bwd, interact bwd, bottom bwd
+    if (flags & DQRM_MODEL_NO_UPDATE) return n;
+    n += dqrm_internal_emb_bwd_sgd_launches(m->tables, batch, next, m->emb_fwd_flags);
+    n += 1 + ((flags & DQRM_MODEL_REQUANT) && (has_tensor_layer(m->bottom) || has_tensor_layer(m->top)) ? 1 : 0);
+    return n;
+}
+
+}  // extern "C"

@@ -1,0 +1,428 @@
+"""The reference's ``DLRM_Net`` (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:214-880) assembled from
+the package's stages, with a training step that is ONE host call.
+
+``DQRMNet`` owns an ``EmbeddingTableSet`` (all tables in one slab), ``bot_l`` / ``top_l`` from
+``create_mlp`` (the reference's state-dict keys) with an ``MLPStack`` each, a ``DotInteraction`` and
+a ``DLRMLoss``.
+
+  * ``forward(dense_x, batch)`` is the autograd composition of those modules: nothing in it is
+    new. It serves training under ``torch.autograd`` and is what the step is tested against.
+  * ``predict(dense_x, batch, labels=None)`` is dqrm_model_fwd: the same forward as one host call.
+  * ``train_step(dense_x, batch, labels, lr)`` is dqrm_model_step: forward, loss, backward, the
+    embedding SGD and the update of both MLP stacks (one launch, requantization included) behind
+    one ABI crossing: no autograd graph, no per-stage tensors, no optimizer. The library calls the
+    stages' own exports in the composition's order, so every buffer holds the composition's bits.
+
+A model is built on its GPU (``device=``) and stays there; there is no CPU path.
+
+World size > 1 is out of scope of ``train_step``'s update: use ``train_step(..., update=False)``,
+which stops after the backward and leaves the gradients in ``p.grad`` and ``model.emb_grad`` for
+the package's DP hooks (``sgd_quantized_gradients_parallel_comm``) to exchange and apply.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib as L
+from .interaction import DotInteraction, out_features
+from .loss import DLRMLoss
+from .mlp import MLPStack, create_mlp
+from .quant_modules_not_quantize_grad import error_check_due, poll_device_errors
+from .tables import EmbeddingTableSet, LookupBatch, _stream_handle
+
+
+def _no_cpu(what, dev):
+    return L.DQRMError(f"DQRMNet.{what} runs on libdqrm's HIP kernels: the model must be on a GPU (got {dev}); "
+                       "there is no CPU path")
+
+
+class DQRMNet(nn.Module):
+    """``DLRM_Net`` with the dot interaction, under the reference's argument names where they apply.
+
+    ln_emb: rows per table; m_spa: the embedding dim; ln_bot / ln_top: the MLPs' widths
+    (``ln_bot[-1] == m_spa``, ``ln_top[0] == m_spa + pairs``, ``ln_top[-1] == 1``); sigmoid_top /
+    sigmoid_bot: the layer a Sigmoid follows (default: the top stack's last layer, none at the
+    bottom); arch_interaction_itself; quantize_bits: None, or 2..16 for the fake-quantized
+    interaction (the reference hard-codes 16); weight_bit, per_channel, full_precision_flag: the
+    MLP layers'; embedding_bit, embedding_full_precision: the tables'; loss_function, loss_weights,
+    loss_threshold: ``DLRMLoss``'s. Tables, then ``bot_l``, then ``top_l`` draw their initial
+    values from numpy's global generator, in the reference's order (emb_weights: given tables).
+
+    ``forward`` returns the top stack's output p ``[B, 1]``; the clamp of ``DLRM_Net.forward`` is
+    ``DLRMLoss``'s (``model.loss(p, T, return_clamped=True)``). ``predict`` without labels returns
+    p; with labels ``(E, Z)``, the loss and the clamped prediction.
+
+    Freshness. ``train_step`` passes DQRM_MODEL_MLP_FRESH only while both ``MLPStack``s are fresh
+    by their own records (mlp.MLPStack: storage, parameter versions, layer settings, the raw-write
+    epoch), and after an updating step re-records them as ``MLPStack.sgd_step`` does (every written
+    parameter's version is bumped). An optimizer step, ``load_state_dict``, ``p.add_()`` are
+    caught; after a write through ``.data`` call ``invalidate()``.
+
+    Prefetch. ``train_step(..., next_batch=nb)`` leaves nb's embedding forward in the workspace
+    (inside the update's launch for small Criteo-form batches). The following ``train_step`` skips
+    its own embedding forward only if its ``batch`` is that very object, the batch size is the
+    same and no table write went through ``model.tables``'s methods or this
+    model's other calls in between; otherwise it runs the forward itself.
+
+    Not built: ``quantize_activation`` (``MLPStack`` does not run those layers), momentum, weight
+    decay, world size > 1 inside the step."""
+
+    def __init__(self, ln_emb, m_spa, ln_bot, ln_top, sigmoid_top=None, sigmoid_bot=-1,
+                 arch_interaction_itself=False, quantize_bits=None, weight_bit=4, embedding_bit=4,
+                 per_channel=False, full_precision_flag=False, embedding_full_precision=False,
+                 quantize_activation=False, loss_function="bce", loss_weights=None, loss_threshold=0.0,
+                 device="cuda", emb_weights=None):
+        super().__init__()
+        if quantize_activation:
+            raise NotImplementedError("DQRMNet does not run quantize_activation=True: MLPStack has no "
+                                      "integer-activation form (use apply_mlp with QuantAct)")
+        self.ln_emb = [int(n) for n in np.asarray(ln_emb).reshape(-1)]
+        self.m_spa = int(m_spa)
+        self.ln_bot = [int(n) for n in np.asarray(ln_bot).reshape(-1)]
+        self.ln_top = [int(n) for n in np.asarray(ln_top).reshape(-1)]
+        T, D = len(self.ln_emb), self.m_spa
+        if T < 1 or len(self.ln_bot) < 2 or len(self.ln_top) < 2:
+            raise ValueError("DQRMNet needs at least one table and one layer per MLP")
+        if self.ln_bot[-1] != D:
+            raise ValueError(f"ln_bot[-1] = {self.ln_bot[-1]} does not match m_spa = {D}: the bottom MLP's output "
+                             "is a feature vector beside the embeddings")
+        want = D + (T + 1) * T // 2 + (T + 1 if arch_interaction_itself else 0)
+        if self.ln_top[0] != want:
+            raise ValueError(f"ln_top[0] = {self.ln_top[0]} does not match the interaction's {want} features "
+                             f"(m_spa + pairs of {T + 1} vectors, arch_interaction_itself={bool(arch_interaction_itself)})")
+        if self.ln_top[-1] != 1:
+            raise ValueError(f"ln_top[-1] must be 1 (got {self.ln_top[-1]})")
+        if len(self.ln_bot) + len(self.ln_top) - 2 > L.DQRM_MLP_MAX_LAYERS:
+            raise ValueError(f"DQRMNet takes at most {L.DQRM_MLP_MAX_LAYERS} MLP layers in all")
+        self.embedding_bit = int(embedding_bit)
+        self.embedding_full_precision = bool(embedding_full_precision)
+        dev = torch.device(device)
+        if emb_weights is None:  # q_m_n_q_g.py:273-275, table after table
+            emb_weights = [torch.from_numpy(np.random.uniform(low=-np.sqrt(1 / n), high=np.sqrt(1 / n),
+                                                              size=(n, D)).astype(np.float32)) for n in self.ln_emb]
+        elif len(emb_weights) != T:
+            raise ValueError("emb_weights needs one tensor per table")
+        if sigmoid_top is None:
+            sigmoid_top = len(self.ln_top) - 2
+        self.bot_l = create_mlp(self.ln_bot, sigmoid_bot, weight_bit=weight_bit, full_precision_flag=full_precision_flag,
+                                per_channel=per_channel)
+        self.top_l = create_mlp(self.ln_top, sigmoid_top, weight_bit=weight_bit, full_precision_flag=full_precision_flag,
+                                per_channel=per_channel)
+        self.interact = DotInteraction(arch_interaction_itself, quantize_bits)
+        self.loss = DLRMLoss(loss_function, loss_weights, loss_threshold)
+        self.tables = None
+        if dev.type == "cuda":
+            self.tables = EmbeddingTableSet(self.ln_emb, D, device=dev, init=None, weights=emb_weights)
+            self.register_buffer("emb_weight", self.tables.W, persistent=True)  # the slab itself
+            self.bot_l.to(dev)
+            self.top_l.to(dev)
+            self.interact.to(dev)
+            self.loss.to(dev)
+            assert want == out_features(T + 1, D, arch_interaction_itself)
+        else:  # a description only: every compute path raises DQRMError
+            self.register_buffer("emb_weight", torch.cat([w.float() for w in emb_weights]), persistent=True)
+        self.bot_stack = MLPStack(self.bot_l)
+        self.top_stack = MLPStack(self.top_l)
+        self.emb_out = None    # forward(): the embedding slab [B, T, D], a leaf whose .grad is demb
+        self.z = None          # train_step(): the clamped prediction [B, 1]
+        self.emb_grad = None   # train_step(update=False): demb [B, T, D], a view of the workspace
+        d = self.__dict__      # plain attributes of the step (nn.Module.__setattr__ is slow per call)
+        d["_ws"] = None        # (tensor, B, max_lookups): the workspace's high-water mark
+        d["_cm"] = None        # (key, L.Model, what it points into)
+        d["_out"] = None       # (B, z, g)
+        d["_grads"] = None     # (ptr key, dw array, db array)
+        d["_lay"] = None       # (L.Model, B, max_lookups, L.ModelLayout)
+        d["_last_flags"] = 0   # the DQRM_MODEL_* flags of the latest train_step
+        d["_prefetched"] = None  # (batch object, tables.write_epoch, B)
+
+    # ------------------------------------------------------------ bookkeeping
+    def _device(self, what):
+        dev = self.emb_weight.device
+        if self.tables is None or dev.type != "cuda":
+            raise _no_cpu(what, dev)
+        if self.emb_weight.data_ptr() != self.tables.W.data_ptr():
+            raise L.DQRMError("DQRMNet was moved or cast after construction: its tables live in the "
+                              "EmbeddingTableSet's slab; build the model with device=...")
+        return dev
+
+    def invalidate(self):
+        """Forget what the model derived from its parameters: both stacks quantize again at the
+        next forward, and a prefetched embedding forward is discarded. Needed only after a write
+        torch cannot see (``p.data.add_()``, a kernel of your own on the tables)."""
+        self.bot_stack.invalidate()
+        self.top_stack.invalidate()
+        self.__dict__["_prefetched"] = None
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        out = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        if self.tables is not None:
+            self._device("load_state_dict")
+            self.tables.refresh_absmax()  # W changed outside the kernels: rebuild the |W| hierarchy
+        self.invalidate()
+        return out
+
+    def _fwd_flags(self):
+        return L.DQRM_FWD_REFRESH_SCALE | (L.DQRM_FWD_FULL_PRECISION if self.embedding_full_precision else 0)
+
+    def _check_inputs(self, dense_x, batch, labels, what):
+        dev = self._device(what)
+        if not isinstance(batch, LookupBatch):
+            raise TypeError(f"DQRMNet.{what} takes a LookupBatch")
+        if batch.num_tables != self.tables.T:
+            raise ValueError("batch has %d tables, set has %d" % (batch.num_tables, self.tables.T))
+        B = batch.num_bags
+        if (not isinstance(dense_x, torch.Tensor) or dense_x.dtype != torch.float32 or dense_x.device != dev
+                or tuple(dense_x.shape) != (B, self.ln_bot[0]) or not dense_x.is_contiguous()):
+            raise ValueError(f"DQRMNet.{what} needs a contiguous float32 [{B}, {self.ln_bot[0]}] dense_x on {dev}")
+        if batch.idx.device != dev:
+            raise ValueError(f"batch on {batch.idx.device} but the model on {dev}")
+        if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.float32
+                                   or labels.device != dev or labels.numel() != B or not labels.is_contiguous()):
+            raise ValueError(f"DQRMNet.{what} needs contiguous float32 labels of {B} elements on {dev}")
+        if not 1 <= B <= L.DQRM_LOSS_MAX_BATCH:
+            raise ValueError(f"DQRMNet.{what} takes 1..{L.DQRM_LOSS_MAX_BATCH} samples (got {B})")
+        return dev, B
+
+    def _c_model(self, kb, kt):
+        """The dqrm_model over the stages' current C structs (rebuilt when any of them moved)."""
+        cb, ct = self.bot_stack._c_struct(kb), self.top_stack._c_struct(kt)
+        loss = self.loss
+        w = loss.loss_ws
+        key = (id(cb), id(ct), id(self.tables.c), loss.loss_function, loss.loss_threshold,
+               None if w is None else w.data_ptr(), self.interact.arch_interaction_itself, self.interact._bits,
+               self.embedding_bit, self.embedding_full_precision)
+        ent = self.__dict__["_cm"]
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        lc = loss._config()
+        m = L.Model()
+        m.tables, m.bottom, m.top, m.loss = C.pointer(self.tables.c), C.pointer(cb), C.pointer(ct), C.pointer(lc)
+        m.interact.num_features, m.interact.dim = self.tables.T + 1, self.tables.D
+        m.interact.self_interaction = int(self.interact.arch_interaction_itself)
+        m.interact.quant_bits = self.interact._bits
+        m.embedding_bit, m.emb_fwd_flags = self.embedding_bit, self._fwd_flags()
+        m.ste, m.repack_bits = int(not self.embedding_full_precision), 0
+        self.__dict__["_cm"] = (key, m, (cb, ct, lc, self.tables.c))
+        return m
+
+    def _prepare(self, what):
+        """The stacks' checks, their keys and the model struct."""
+        if self.loss.loss_function == "wbce" and self.loss.loss_ws.device != self.emb_weight.device:
+            raise ValueError("DLRMLoss.loss_ws is not on the model's device")
+        self.bot_stack._prepare()
+        self.top_stack._prepare()
+        kb, kt = self.bot_stack._key(), self.top_stack._key()
+        return kb, kt, self._c_model(kb, kt)
+
+    def _workspace(self, m, B, max_lookups, dev, keep=0):
+        """One device buffer per (B, max_lookups) high-water mark; a smaller batch is cut from the
+        same buffer. A new buffer takes over the first `keep` bytes of the old one (a prefetched
+        slab, which sits at offset 0 of every cut); without them it holds no prefetched forward."""
+        ent = self.__dict__["_ws"]
+        if ent is not None and ent[1] >= B and ent[2] >= max_lookups and ent[0].device == dev:
+            return ent[0]
+        hb = max(B, ent[1]) if ent is not None else B
+        hl = max(max_lookups, ent[2]) if ent is not None else max_lookups
+        need = self.tables.lib.dqrm_model_workspace_bytes(C.byref(m), hb, hl)
+        if need == 0:
+            L.check(L.DQRM_E_INVALID, "dqrm_model_workspace_bytes")
+        ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        if keep and ent is not None and ent[0].device == dev:
+            ws[:keep].copy_(ent[0][:keep])
+        else:
+            self.__dict__["_prefetched"] = None
+        self.__dict__["_ws"] = (ws, hb, hl)
+        self.emb_grad = None
+        return ws
+
+    def _layout(self, m, B, max_lookups):
+        ent = self.__dict__["_lay"]
+        if ent is not None and ent[0] is m and ent[1] == B and ent[2] == max_lookups:
+            return ent[3]
+        lay = L.ModelLayout()
+        L.check(self.tables.lib.dqrm_model_workspace_layout(C.byref(m), B, max_lookups, C.byref(lay)),
+                "dqrm_model_workspace_layout")
+        self.__dict__["_lay"] = (m, B, max_lookups, lay)
+        return lay
+
+    def _view(self, ws, m, B, max_lookups, name):
+        """A part of the workspace as a float32 tensor: slab / demb [B, T, D], r / dr [B, R],
+        dx [B, D], p [B, 1]."""
+        T, D = self.tables.T, self.tables.D
+        shape = {"slab": (B, T, D), "demb": (B, T, D), "r": (B, self.ln_top[0]), "dr": (B, self.ln_top[0]),
+                 "dx": (B, D), "p": (B, 1)}[name]
+        off = getattr(self._layout(m, B, max_lookups), name)
+        n = 4 * int(np.prod(shape))
+        return ws[off: off + n].view(torch.float32).view(shape)
+
+    def _outputs(self, B, dev):
+        ent = self.__dict__["_out"]
+        if ent is None or ent[0] != B or ent[1].device != dev:
+            ent = (B, torch.empty((B, 1), dtype=torch.float32, device=dev),
+                   torch.empty(B, dtype=torch.float32, device=dev))
+            self.__dict__["_out"] = ent
+        return ent[1], ent[2]
+
+    def _grad_arrays(self):
+        """Persistent gradient tensors bound as the parameters' ``.grad``, and the two host arrays
+        of their device pointers (bottom's layers, then top's)."""
+        layers = self.bot_stack.layers + self.top_stack.layers
+        ptrs = []
+        for l in layers:
+            for p in (l.weight, l.bias):
+                g = p.grad
+                if (g is None or g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape
+                        or not g.is_contiguous()):
+                    g = p.grad = torch.zeros_like(p)
+                ptrs.append(g.data_ptr())
+        key = tuple(ptrs)
+        ent = self.__dict__["_grads"]
+        if ent is None or ent[0] != key:
+            A = C.c_void_p * len(layers)
+            ent = (key, A(*ptrs[0::2]), A(*ptrs[1::2]))
+            self.__dict__["_grads"] = ent
+        return ent[1], ent[2]
+
+    def _poll(self):
+        if error_check_due(self) and not torch.cuda.is_current_stream_capturing():
+            poll_device_errors(self.tables)
+
+    # ------------------------------------------------------------ the composition
+    def forward(self, dense_x, batch):
+        """p ``[B, 1]``: the bottom stack, the tables' fused forward, the interaction and the top
+        stack as autograd nodes. ``model.emb_out`` is the embedding slab ``[B, T, D]``, a leaf: after
+        ``backward()`` its ``.grad`` is what ``model.tables.backward_sgd(batch, grad, lr,
+        layout="btd")`` takes; the stacks are updated with ``sgd_step``."""
+        self._device("forward")
+        x = self.bot_stack(dense_x)
+        slab = self.tables.forward(batch, bits=self.embedding_bit, refresh_scale=True,
+                                   full_precision=self.embedding_full_precision, layout="btd")
+        if torch.is_grad_enabled():
+            slab.requires_grad_(True)
+        self.emb_out = slab
+        return self.top_stack(self.interact(x, slab))
+
+    # ------------------------------------------------------------ one host call
+    def _on(self, dev, fn, *args):
+        if dev.index != torch.cuda.current_device():
+            with torch.cuda.device(dev):
+                return fn(*args)
+        return fn(*args)
+
+    def predict(self, dense_x, batch, labels=None):
+        """The forward as ONE host call (dqrm_model_fwd): p ``[B, 1]`` without labels, ``(E, Z)``
+        with them: the 0-dim loss and the clamped prediction. Quantizes the MLP weights only when
+        the stacks are not fresh (``requantize()`` makes them so)."""
+        dev, B = self._check_inputs(dense_x, batch, labels, "predict")
+        return self._on(dev, self._predict, dense_x, batch, labels, dev, B)
+
+    def _predict(self, dense_x, batch, labels, dev, B):
+        kb, kt, m = self._prepare("predict")
+        fresh = self.bot_stack._fresh is not None and self.top_stack._fresh is not None \
+            and self.bot_stack._fresh == self.bot_stack._state(kb) and self.top_stack._fresh == self.top_stack._state(kt)
+        ws = self._workspace(m, B, batch.max_lookups, dev)
+        self.__dict__["_prefetched"] = None  # the slab is overwritten
+        self._poll()
+        loss = z = None
+        if labels is not None:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            z = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        L.check(self.tables.lib.dqrm_model_fwd(
+            C.byref(m), C.byref(batch.c), L.DQRM_MODEL_MLP_FRESH if fresh else 0, dense_x.data_ptr(),
+            None if labels is None else labels.data_ptr(), None if loss is None else loss.data_ptr(),
+            None if z is None else z.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle()), "dqrm_model_fwd")
+        if labels is not None:
+            return loss, z
+        return self._view(ws, m, B, batch.max_lookups, "p").clone()
+
+    def requantize(self):
+        """Quantize both stacks' weights now and mark them fresh (``MLPStack.requantize``)."""
+        self._device("requantize")
+        self.bot_stack.requantize()
+        self.top_stack.requantize()
+
+    def step_launches(self, batch, next_batch=None, update=True, prefetched=False, fresh=None):
+        """dqrm_model_step_launches for a ``train_step`` with these arguments (fresh None: the
+        stacks' current state)."""
+        self._device("step_launches")
+        kb, kt, m = self._prepare("step_launches")
+        if fresh is None:
+            fresh = self.bot_stack.is_fresh() and self.top_stack.is_fresh()
+        flags = (L.DQRM_MODEL_MLP_FRESH if fresh else 0) | (L.DQRM_MODEL_REQUANT if update else L.DQRM_MODEL_NO_UPDATE) \
+            | (L.DQRM_MODEL_EMB_READY if prefetched else 0)
+        n = self.tables.lib.dqrm_model_step_launches(C.byref(m), C.byref(batch.c),
+                                                     None if next_batch is None else C.byref(next_batch.c), flags)
+        if n < 0:
+            L.check(n, "dqrm_model_step_launches")
+        return n
+
+    def train_step(self, dense_x, batch, labels, lr, next_batch=None, update=True):
+        """One training step as ONE host call (dqrm_model_step); returns the 0-dim loss tensor.
+        ``model.z`` then holds the clamped prediction ``[B, 1]`` (overwritten by the next step).
+
+        update=True: SGD with ``lr`` on the tables (dqrm_emb_bwd_sgd) and on both MLP stacks, which
+        are requantized in the same launch and are fresh afterwards. next_batch: the batch of the
+        following step; its embedding forward is left in the workspace (see the class docstring).
+        update=False: the step stops after the backward; no parameter, table, scale or integer
+        buffer is written, ``p.grad`` of every MLP parameter holds its gradient and
+        ``model.emb_grad`` (set by every step) is the ``[B, T, D]`` gradient of the embedding slab (a
+        view of the workspace, valid until the next call): the route for world size > 1, where the DP hooks
+        take it from there. ``next_batch`` needs update=True.
+
+        The MLP gradients are written into persistent tensors bound as ``p.grad`` (overwritten,
+        not accumulated)."""
+        dev, B = self._check_inputs(dense_x, batch, labels, "train_step")
+        if next_batch is not None:
+            if not update:
+                raise ValueError("DQRMNet.train_step: next_batch needs update=True")
+            if not isinstance(next_batch, LookupBatch) or next_batch.num_tables != self.tables.T:
+                raise ValueError("DQRMNet.train_step: next_batch must be a LookupBatch of the model's tables")
+            if next_batch.num_bags != B or next_batch.idx.device != dev:
+                raise ValueError(f"DQRMNet.train_step: next_batch has {next_batch.num_bags} bags, batch {B} "
+                                 "(the prefetched forward shares the slab)")
+        return self._on(dev, self._train_step, dense_x, batch, labels, float(lr), next_batch, bool(update), dev, B)
+
+    def _train_step(self, dense_x, batch, labels, lr, next_batch, update, dev, B):
+        bot, top, tables = self.bot_stack, self.top_stack, self.tables
+        kb, kt, m = self._prepare("train_step")
+        fresh = bot._fresh is not None and top._fresh is not None and bot._fresh == bot._state(kb) \
+            and top._fresh == top._state(kt)
+        pf = self.__dict__["_prefetched"]
+        ready = pf is not None and pf[0] is batch and pf[1] == tables.write_epoch and pf[2] == B
+        # sized for the next batch too, so that its step finds its slab where this one leaves it
+        ml = batch.max_lookups if next_batch is None else max(batch.max_lookups, next_batch.max_lookups)
+        ws = self._workspace(m, B, ml, dev, keep=4 * B * tables.T * tables.D if ready else 0)
+        self.__dict__["_prefetched"] = None
+        flags = (L.DQRM_MODEL_MLP_FRESH if fresh else 0) | (L.DQRM_MODEL_EMB_READY if ready else 0) \
+            | (L.DQRM_MODEL_REQUANT if update else L.DQRM_MODEL_NO_UPDATE)
+        self.__dict__["_last_flags"] = flags
+        z, g = self._outputs(B, dev)
+        dw, db = self._grad_arrays()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        self._poll()
+        if update:  # whatever happens from here on, the integers are no longer known to be current
+            bot._fresh = top._fresh = None
+        rc = tables.lib.dqrm_model_step(
+            C.byref(m), C.byref(batch.c), None if next_batch is None else C.byref(next_batch.c), flags,
+            dense_x.data_ptr(), labels.data_ptr(), lr, loss.data_ptr(), z.data_ptr(), g.data_ptr(), dw, db,
+            ws.data_ptr(), ws.numel(), _stream_handle())
+        L.check(rc, "dqrm_model_step")
+        self.__dict__["z"] = z
+        self.__dict__["emb_grad"] = self._view(ws, m, B, batch.max_lookups, "demb")
+        if not update:
+            return loss
+        tables.write_epoch += 1
+        for l in bot.layers + top.layers:  # the kernel wrote them: what autograd saved of them is stale
+            torch.autograd.graph.increment_version(l.weight)
+            torch.autograd.graph.increment_version(l.bias)
+        bot._fresh, top._fresh = bot._state(kb), top._state(kt)
+        if next_batch is not None:
+            self.__dict__["_prefetched"] = (next_batch, tables.write_epoch, B)
+        return loss
+
+
+__all__ = ["DQRMNet"]

@@ -242,6 +242,9 @@ class EmbeddingTableSet:
         # per-table arrival counters of the in-launch finalize, one per 256 bytes
         self.sync = torch.zeros(T * L.DQRM_SYNC_STRIDE, dtype=torch.int32, device=dev)
         self._bws: torch.Tensor | None = None  # backward workspace, grown to the largest batch seen
+        # counts this object's calls that rewrite W: a caller holding something derived from the
+        # tables (model.DQRMNet's prefetched forward) compares it before trusting that
+        self.write_epoch = 0
         self._err_host: torch.Tensor | None = None  # pinned snapshot of the error word (poll_errors)
         self._err_evt = None
         self._err_pending = False
@@ -296,6 +299,7 @@ class EmbeddingTableSet:
         v.bdirty = self.bdirty[bb:]
         v.sync = self.sync[t * L.DQRM_SYNC_STRIDE: (t + 1) * L.DQRM_SYNC_STRIDE]
         v._bws, v._err_host, v._err_evt, v._err_pending = None, None, None, False
+        v.write_epoch = 0
         v._rows_host = (C.c_int64 * 1)(n)
         v._c = L.TableSet(
             1, self.D, n, nb, ns,
@@ -317,6 +321,7 @@ class EmbeddingTableSet:
     # ------------------------------------------------------------------ maintenance
     def refresh_absmax(self) -> None:
         """Recompute the |W| max hierarchy from W (after any external write to W)."""
+        self.write_epoch = getattr(self, "write_epoch", 0) + 1
         L.check(self.lib.dqrm_refresh_absmax(C.byref(self._c), _stream_handle()), "dqrm_refresh_absmax")
 
     def repack_all(self, bits: int = 4) -> None:
@@ -462,6 +467,7 @@ class EmbeddingTableSet:
                      repack: bool = False, layout: str = "tbd") -> None:
         """Fused STE + sparse backward + SGD (torch.optim.SGD semantics, in lookup order)."""
         st, sb = self._dy_strides(dy, layout, self.T, batch.num_bags, self.D)
+        self.write_epoch += 1
         L.check(
             self.lib.dqrm_emb_bwd_sgd(C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, int(ste),
                                       float(lr), 4 if repack else 0, *self._ws_args(batch), _stream_handle()),
@@ -482,6 +488,7 @@ class EmbeddingTableSet:
             out = torch.empty((T, B, D) if layout == "tbd" else (B, T, D), dtype=torch.float32, device=self.device)
         ost, osb = (B * D, D) if layout == "tbd" else (D, T * D)
         st, sb = self._dy_strides(dy, dy_layout, self.T, batch.num_bags, self.D)
+        self.write_epoch += 1
         L.check(
             self.lib.dqrm_emb_bwd_sgd_fwd(
                 C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, int(ste), float(lr), 4 if repack else 0,
@@ -505,6 +512,7 @@ class EmbeddingTableSet:
         """W.add_(-lr * grad) with the rank's own uncoalesced gradient, product rounded, in
         lookup order (ranking-range 32-bit tables, s_q_g_p_c.py:615-616); table_mask int32 [T]."""
         st, sb = self._dy_strides(dy, layout, self.T, batch.num_bags, self.D)
+        self.write_epoch += 1
         L.check(
             self.lib.dqrm_emb_local_update(C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, int(ste),
                                            float(lr), _ptr(table_mask), 4 if repack else 0,
@@ -516,6 +524,7 @@ class EmbeddingTableSet:
         """Rows (slab ids, device i64) rewritten outside the kernels, e.g. by torch.optim.SGD
         on the lookup_grad COO: refresh their maxima in the |W| hierarchy (and INT4 rows)."""
         rows = rows.to(device=self.device, dtype=torch.int64).contiguous()
+        self.write_epoch += 1
         L.check(self.lib.dqrm_rows_changed(C.byref(self._c), _ptr(rows), rows.numel(), 4 if repack else 0,
                                            _stream_handle()), "dqrm_rows_changed")
 
@@ -593,6 +602,7 @@ class EmbeddingTableSet:
         """World size 1: backward_coalesce + the local quantized update (dqrm_apply_local),
         one launch for Criteo-form batches (dqrm_emb_bwd_apply_local); same results."""
         st, sb = self._dy_strides(dy, layout, self.T, batch.num_bags, self.D)
+        self.write_epoch += 1
         L.check(
             self.lib.dqrm_emb_bwd_apply_local(
                 C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, int(ste), _ptr(ws.slot_cap_base),
@@ -637,6 +647,7 @@ class EmbeddingTableSet:
             out = torch.empty((T, B, D) if layout == "tbd" else (B, T, D), dtype=torch.float32, device=self.device)
         ost, osb = (B * D, D) if layout == "tbd" else (D, T * D)
         st, sb = self._dy_strides(dy, dy_layout, self.T, batch.num_bags, self.D)
+        self.write_epoch += 1
         L.check(
             self.lib.dqrm_emb_bwd_apply_fwd_local(
                 C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, int(ste), _ptr(ws.slot_cap_base),

@@ -83,7 +83,11 @@ extern "C" {
                                   DQRM_LOSS_*: dqrm_loss_fwd, dqrm_loss_bwd;
                                   likewise within 12: a whole MLP stack per call, dqrm_mlp
                                   (MLPStack): dqrm_mlp_fwd, dqrm_mlp_bwd_scratch_bytes,
-                                  dqrm_mlp_bwd, dqrm_mlp_sgd_workspace_bytes, dqrm_mlp_sgd */
+                                  dqrm_mlp_bwd, dqrm_mlp_sgd_workspace_bytes, dqrm_mlp_sgd;
+                                  likewise within 12: the whole model per call, dqrm_model (DQRMNet):
+                                  dqrm_mlp_sgd_multi_workspace_bytes, dqrm_mlp_sgd_multi,
+                                  dqrm_model_workspace_bytes, dqrm_model_workspace_layout,
+                                  dqrm_model_fwd, dqrm_model_step, dqrm_model_step_launches */
 
 /* status codes */
 #define DQRM_OK            0
@@ -755,6 +759,19 @@ size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* stack);
 int dqrm_mlp_sgd(const dqrm_mlp* stack, uint32_t flags, const float* const* dw, const float* const* db,
                  const float* const* gscale, float lr, void* workspace, size_t workspace_bytes, void* stream);
 
+/* dqrm_mlp_sgd on several stacks (a model's bottom and top MLP) in ONE launch: the same kernels
+ * over the rows of all the stacks' layers, so per (layer, row) the same formulas, roundings and
+ * bits as dqrm_mlp_sgd on each stack alone. stacks: HOST array of num_stacks stacks, each checked
+ * as dqrm_mlp_sgd checks it (its own width chain included); their layers number at most
+ * DQRM_MLP_MAX_LAYERS in all. dw / db / gscale: HOST arrays over the layers of stacks[0], then
+ * stacks[1], ... Two launches when DQRM_MLP_REQUANT meets a quantized per-tensor layer in any of
+ * them; the workspace is then 4 bytes per weight row of ALL the stacks
+ * (dqrm_mlp_sgd_multi_workspace_bytes; 0 otherwise, and 0 for arguments it rejects). */
+size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num_stacks);
+int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
+                       const float* const* db, const float* const* gscale, float lr, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * QuantAct: fake-quantized activations with a running range (quantization_supp/
  * quant_modules_not_quantize_grad.py:541-725), csrc/dqrm_act.hip. Symmetric, one scale for the
@@ -915,6 +932,99 @@ int dqrm_interact_fwd(const dqrm_interact* cfg, const float* x, const float* emb
  * no launch). One launch. scale: the one the forward used. */
 int dqrm_interact_bwd(const dqrm_interact* cfg, const float* x, const float* emb, const float* dr, int64_t B,
                       const float* scale, float* dx, float* demb, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * DQRMNet: the whole DLRM (DLRM_Net.forward, dlrm_s_pytorch_tb_dp_one_parallel_comm.py:805-880,
+ * and one iteration of its training loop at world size 1) per host call, csrc/dqrm_model.hip.
+ * dqrm_model_fwd and dqrm_model_step contain no arithmetic: they validate the whole call and then
+ * call the exports above in the order a stage-by-stage caller would, so every buffer they write
+ * holds what that chain of calls writes, bit for bit. What they save is the host's work per stage.
+ *
+ * The struct is HOST memory; `tables`, `bottom`, `top` and `loss` point to host structs as the
+ * stage calls take them. interact.num_features must be tables->num_tables + 1 and interact.dim
+ * tables->dim; interact.emb_stride_b / _f are ignored (the library reads the embedding slab it lays
+ * out itself, [B][T][D]). bottom's last width must be D, top's first
+ * dqrm_interact_out_features(T + 1, D, self_interaction), top's last 1. bottom and top have at most
+ * DQRM_MLP_MAX_LAYERS layers together (their update is one dqrm_mlp_sgd_multi).
+ *
+ * Memory: nothing is allocated. The caller passes one device workspace (16-byte aligned, contents
+ * irrelevant) of dqrm_model_workspace_bytes(model, B, max_lookups) bytes, which the library cuts
+ * into: the embedding slab [B][T][D] (offset 0), every layer's output, r and dr [B][D + P], dx
+ * [B][D], demb [B][T][D], the MLP backward scratch, the embedding backward's sort workspace
+ * (dqrm_bwd_workspace_bytes), the interaction's scale word and the per-tensor layers' row maxima.
+ * The cut depends on (B, batch->max_lookups) alone and the size grows with both, so one buffer
+ * sized for the largest batch serves every smaller one. dqrm_model_workspace_layout tells where
+ * the slab, r, p (the top stack's output [B]), dr, dx and demb sit (byte offsets).
+ *
+ * dqrm_model_fwd (inference): dqrm_emb_fwd into the slab; dqrm_mlp_fwd(bottom, x);
+ * dqrm_interact_scale (quant_bits != 0) and dqrm_interact_fwd; dqrm_mlp_fwd(top); and, labels
+ * given, dqrm_loss_fwd(p, labels) with g == NULL writing loss[1] and z[B] (nullable). labels ==
+ * NULL: no loss launch, loss and z are not touched; p is in the workspace.
+ *
+ * dqrm_model_step (one training step): the forward as above with g[B] written;
+ * dqrm_mlp_bwd(top, dy = g) -- loss.backward()'s upstream gradient is 1.0 and 1.0f * g is g bit
+ * for bit, so dqrm_loss_bwd is not launched --; dqrm_interact_bwd; dqrm_mlp_bwd(bottom, dx ==
+ * NULL); dqrm_emb_bwd_sgd on demb; dqrm_mlp_sgd_multi(bottom, top). dw / db: HOST arrays of device
+ * pointers over bottom's layers, then top's. Flags:
+ *   DQRM_MODEL_MLP_FRESH  both stacks' integers are current: the forwards run DQRM_MLP_FRESH
+ *   DQRM_MODEL_REQUANT    the update refreshes the integers (DQRM_MLP_REQUANT)
+ *   DQRM_MODEL_NO_UPDATE  stop after the backward: dw, db and demb are the caller's (the DP hooks),
+ *                         no parameter is written; `next` must be NULL
+ *   DQRM_MODEL_EMB_READY  the slab already holds this batch's forward (the previous step's `next`):
+ *                         dqrm_emb_fwd is skipped
+ *   next != NULL          the embedding update is dqrm_emb_bwd_sgd_fwd, which leaves next's forward
+ *                         in the slab (one launch when dqrm_bwd_sgd_fwd_is_one_launch); next must
+ *                         have batch's num_bags
+ * dqrm_model_fwd takes DQRM_MODEL_MLP_FRESH and DQRM_MODEL_EMB_READY.
+ *
+ * dqrm_model_step_launches: the kernel launches the step will issue (memsets not counted), <0 on
+ * arguments the step rejects (workspace and tensor pointers apart). With L = L_bottom + L_top
+ * per-channel fresh layers, plain interaction: 3L + 5 (26 for the Kaggle stacks, 4 + 3 layers);
+ * - 1 with DQRM_MODEL_EMB_READY; + 1 per quantized per-channel layer and + 2 per per-tensor one
+ * when not fresh; + 1 for the quantized interaction's scale; + 1 when DQRM_MODEL_REQUANT meets a
+ * per-tensor layer; + 1 when next's forward is a launch of its own; with DQRM_MODEL_NO_UPDATE the
+ * two update launches are absent.
+ *
+ * The whole call is validated before the first launch; a rejected call writes nothing.
+ * DQRM_E_INVALID: a null struct or member, what each stage's export rejects, the width rules
+ * above (dqrm_batch carries no table count: its arrays are read as the set's T tables', and a
+ * caller that knows the count compares it itself), B = batch->num_bags < 1 or > 2^20, unknown flags, null x / labels / loss / g / dw / db, next
+ * with another num_bags or with DQRM_MODEL_NO_UPDATE. DQRM_E_WORKSPACE: a null, misaligned or
+ * short workspace. No call allocates, synchronises or reads back.
+ * ------------------------------------------------------------------------------ */
+typedef struct dqrm_model {
+    const dqrm_table_set* tables;
+    const dqrm_mlp* bottom;
+    const dqrm_mlp* top;
+    const dqrm_loss* loss;
+    dqrm_interact interact;
+    int32_t  embedding_bit;   /* dqrm_emb_fwd's bits */
+    uint32_t emb_fwd_flags;   /* DQRM_FWD_* of every embedding forward */
+    int32_t  ste;             /* dqrm_emb_bwd_sgd's ste (0 with DQRM_FWD_FULL_PRECISION) */
+    int32_t  repack_bits;     /* dqrm_emb_bwd_sgd's repack_bits */
+} dqrm_model;
+
+typedef struct dqrm_model_layout {  /* byte offsets into the workspace */
+    size_t slab, r, p, dr, dx, demb;
+    size_t total;                   /* dqrm_model_workspace_bytes */
+} dqrm_model_layout;
+
+#define DQRM_MODEL_MLP_FRESH 1u
+#define DQRM_MODEL_REQUANT   2u
+#define DQRM_MODEL_NO_UPDATE 4u
+#define DQRM_MODEL_EMB_READY 8u
+
+/* 0 for arguments it rejects (dqrm_last_error says why) */
+size_t dqrm_model_workspace_bytes(const dqrm_model* model, int64_t B, int64_t max_lookups);
+int dqrm_model_workspace_layout(const dqrm_model* model, int64_t B, int64_t max_lookups, dqrm_model_layout* out);
+int dqrm_model_fwd(const dqrm_model* model, const dqrm_batch* batch, uint32_t flags, const float* x,
+                   const float* labels, float* loss, float* z, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int dqrm_model_step(const dqrm_model* model, const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags,
+                    const float* x, const float* labels, float lr, float* loss, float* z, float* g,
+                    float* const* dw, float* const* db, void* workspace, size_t workspace_bytes, void* stream);
+int dqrm_model_step_launches(const dqrm_model* model, const dqrm_batch* batch, const dqrm_batch* next,
+                             uint32_t flags);
 
 /* ---------------------------------------------------------------------------------
  * Row-wise PTQ formats of the reference's inference path.
