@@ -29,39 +29,22 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int RWG = 1024;                   // range kernels: threads per workgroup
 constexpr int EWG = 256;                    // elementwise kernels: threads per workgroup
 constexpr int64_t kOneGroupMax = 16384;     // up to here the update workgroup reads x itself
 constexpr int kMaxGroups = 1024;            // partial workgroups (the workspace holds 2 floats each)
 constexpr int64_t kPartialPerGroup = 16384; // elements a partial workgroup takes before the grid is capped
 constexpr int kMaxElemGroups = 1 << 16;     // elementwise grid cap (grid-stride beyond)
-
-int act_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define AHIP_TRY(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return act_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
 
 __device__ __forceinline__ void wave_minmax(float& lo, float& hi) {
 #pragma unroll
@@ -143,9 +126,8 @@ __global__ void __launch_bounds__(RWG) k_act_range_update(const float* __restric
     }
 }
 
-__device__ __forceinline__ float act_quant1(float v, float rcp, float s, float lo, float hi) {
-    const float q = fminf(fmaxf(rintf(rcp * v + 0.0f), lo), hi);
-    return q * s;
+DQRM_INLINE float quant_dequant(float v, float rcp, float s, float lo, float hi) {
+    return fake_quant(v, rcp, lo, hi) * s;
 }
 
 // launch 3: scale = clamp(max(|x_min|, |x_max|), 1e-8) / n; y = clamp(round(1/scale * x + 0)) * scale.
@@ -165,12 +147,12 @@ __global__ void __launch_bounds__(EWG) k_act_quantize(const float* __restrict__ 
         float4* __restrict__ y4 = reinterpret_cast<float4*>(y);
         for (int64_t e = t; e < n4; e += stride) {
             const float4 v = x4[e];
-            y4[e] = make_float4(act_quant1(v.x, rcp, s, lo, hi), act_quant1(v.y, rcp, s, lo, hi),
-                                act_quant1(v.z, rcp, s, lo, hi), act_quant1(v.w, rcp, s, lo, hi));
+            y4[e] = make_float4(quant_dequant(v.x, rcp, s, lo, hi), quant_dequant(v.y, rcp, s, lo, hi),
+                                quant_dequant(v.z, rcp, s, lo, hi), quant_dequant(v.w, rcp, s, lo, hi));
         }
-        for (int64_t e = n4 * 4 + t; e < numel; e += stride) y[e] = act_quant1(x[e], rcp, s, lo, hi);
+        for (int64_t e = n4 * 4 + t; e < numel; e += stride) y[e] = quant_dequant(x[e], rcp, s, lo, hi);
     } else {
-        for (int64_t e = t; e < numel; e += stride) y[e] = act_quant1(x[e], rcp, s, lo, hi);
+        for (int64_t e = t; e < numel; e += stride) y[e] = quant_dequant(x[e], rcp, s, lo, hi);
     }
 }
 
@@ -198,36 +180,36 @@ int partial_groups(int64_t numel) {
 extern "C" {
 
 int64_t dqrm_act_quant_workspace_bytes(int64_t numel) {
-    if (numel < 0) return act_error(DQRM_E_INVALID, "dqrm_act_quant_workspace_bytes: negative numel");
+    if (numel < 0) return set_error(DQRM_E_INVALID, "dqrm_act_quant_workspace_bytes: negative numel");
     return numel > kOneGroupMax ? (int64_t)kMaxGroups * 2 * (int64_t)sizeof(float) : 0;
 }
 
 int dqrm_act_quant_fwd(const dqrm_act_quant* q, const float* x, int64_t numel, float* y, void* workspace,
                        void* stream) {
     const char* what = "dqrm_act_quant_fwd";
-    if (!q) return act_error(DQRM_E_INVALID, "%s: null dqrm_act_quant", what);
+    if (!q) return set_error(DQRM_E_INVALID, "%s: null dqrm_act_quant", what);
     if (q->activation_bit < 2 || q->activation_bit > 32)
-        return act_error(DQRM_E_INVALID, "%s: activation_bit must be 2..32 (got %d)", what, q->activation_bit);
-    if (!q->x_min || !q->x_max || !q->scale) return act_error(DQRM_E_INVALID, "%s: null x_min / x_max / scale", what);
-    if (numel < 0) return act_error(DQRM_E_INVALID, "%s: negative numel", what);
+        return set_error(DQRM_E_INVALID, "%s: activation_bit must be 2..32 (got %d)", what, q->activation_bit);
+    if (!q->x_min || !q->x_max || !q->scale) return set_error(DQRM_E_INVALID, "%s: null x_min / x_max / scale", what);
+    if (numel < 0) return set_error(DQRM_E_INVALID, "%s: negative numel", what);
     if (numel == 0) return DQRM_OK;
-    if (!x) return act_error(DQRM_E_INVALID, "%s: null x", what);
+    if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);
     if (!y && !q->running_stat)
-        return act_error(DQRM_E_INVALID, "%s: null y (a range-only call) needs running_stat", what);
+        return set_error(DQRM_E_INVALID, "%s: null y (a range-only call) needs running_stat", what);
     const int groups = q->running_stat ? partial_groups(numel) : 0;
     if (groups > 0 && !workspace)
-        return act_error(DQRM_E_INVALID, "%s: null workspace (dqrm_act_quant_workspace_bytes(%lld) bytes needed)",
+        return set_error(DQRM_E_INVALID, "%s: null workspace (dqrm_act_quant_workspace_bytes(%lld) bytes needed)",
                          what, (long long)numel);
     hipStream_t st = (hipStream_t)stream;
     if (q->running_stat) {
         float* part = (float*)workspace;
         if (groups > 0) {
             hipLaunchKernelGGL(k_act_range_partial, dim3((unsigned)groups), dim3(RWG), 0, st, x, numel, part);
-            AHIP_TRY(hipGetLastError());
+            DQRM_HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_act_range_update, dim3(1), dim3(RWG), 0, st, x, numel, part, groups, q->momentum,
                            q->one_minus_momentum, q->x_min, q->x_max);
-        AHIP_TRY(hipGetLastError());
+        DQRM_HIP_TRY(hipGetLastError());
     }
     if (y) {
         const int64_t nq = ((int64_t)1 << (q->activation_bit - 1)) - 1;
@@ -238,19 +220,19 @@ int dqrm_act_quant_fwd(const dqrm_act_quant* q, const float* x, int64_t numel, f
         else
             hipLaunchKernelGGL(k_act_quantize<false>, dim3(elem_groups(numel)), dim3(EWG), 0, st, x, numel, y,
                                q->x_min, q->x_max, q->scale, n, lo, hi);
-        AHIP_TRY(hipGetLastError());
+        DQRM_HIP_TRY(hipGetLastError());
     }
     return DQRM_OK;
 }
 
 int dqrm_act_quant_bwd(const float* scale, const float* dy, int64_t numel, float* dx, void* stream) {
     const char* what = "dqrm_act_quant_bwd";
-    if (!scale) return act_error(DQRM_E_INVALID, "%s: null scale", what);
-    if (numel < 0) return act_error(DQRM_E_INVALID, "%s: negative numel", what);
+    if (!scale) return set_error(DQRM_E_INVALID, "%s: null scale", what);
+    if (numel < 0) return set_error(DQRM_E_INVALID, "%s: negative numel", what);
     if (numel == 0) return DQRM_OK;
-    if (!dy || !dx) return act_error(DQRM_E_INVALID, "%s: null dy / dx", what);
+    if (!dy || !dx) return set_error(DQRM_E_INVALID, "%s: null dy / dx", what);
     hipLaunchKernelGGL(k_act_bwd, dim3(elem_groups(numel)), dim3(EWG), 0, (hipStream_t)stream, dy, numel, dx, scale);
-    AHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 

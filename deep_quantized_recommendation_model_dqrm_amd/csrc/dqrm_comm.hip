@@ -16,14 +16,12 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <mutex>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
 
 namespace {
 
@@ -63,9 +61,7 @@ Rccl& rccl() {
 }
 
 int fail(int code, const char* what, const char* detail) {
-    char buf[384];
-    snprintf(buf, sizeof(buf), "%s: %s", what, detail);
-    return dqrm_internal_set_error(code, buf);
+    return dqrm_internal::set_error(code, "%s: %s", what, detail);
 }
 
 int rccl_fail(const char* what, RcclResult e) {

@@ -25,35 +25,18 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int DWG = 256;                 // threads per workgroup
 constexpr int CPW = DWG / WAVE;          // channels per workgroup (one per wave)
-
-int dense_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define DHIP_TRY(expr)                                                                       \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return dense_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
 
 struct DenseArgs {
     int C;
@@ -62,18 +45,6 @@ struct DenseArgs {
     const int32_t* len;
     const int64_t* wire_off;
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-// torch.round (half to even) == rintf; clamp to [lo, hi]
-__device__ __forceinline__ float quant1(float g, float rcp, float lo, float hi) {
-    const float q = rintf(rcp * g + 0.0f);
-    return fminf(fmaxf(q, lo), hi);
-}
 
 template <int WT> struct Wire;
 template <> struct Wire<DQRM_WIRE_F16> {
@@ -129,7 +100,7 @@ __global__ void __launch_bounds__(DWG) k_dense_quant(DenseArgs a, const float* _
     s = s * inv_n;
     if (lane == 0) s_avg[c] = s;
     const float rcp = 1.0f / s;
-    for (int j = lane; j < n; j += WAVE) w[j] = Wire<WT>::enc(quant1(g[j], rcp, lo, hi));
+    for (int j = lane; j < n; j += WAVE) w[j] = Wire<WT>::enc(fake_quant(g[j], rcp, lo, hi));
 }
 
 // grad = 0 + sum * (1/N)  (quantized) / sum * (1/N)  (FP32)
@@ -163,17 +134,17 @@ __global__ void __launch_bounds__(DWG) k_dense_update(DenseArgs a, const float* 
 }
 
 int check_dense(const dqrm_dense_set* s) {
-    if (!s) return dense_error(DQRM_E_INVALID, "dqrm_dense: null dense set");
+    if (!s) return set_error(DQRM_E_INVALID, "dqrm_dense: null dense set");
     if (s->num_channels < 0 || s->total_elems < 0)
-        return dense_error(DQRM_E_INVALID, "dqrm_dense: negative channel/element count");
+        return set_error(DQRM_E_INVALID, "dqrm_dense: negative channel/element count");
     if (s->num_channels > 0 && (!s->grad || !s->param || !s->len || !s->wire_off))
-        return dense_error(DQRM_E_INVALID, "dqrm_dense: null channel table");
+        return set_error(DQRM_E_INVALID, "dqrm_dense: null channel table");
     return DQRM_OK;
 }
 
 int check_bits(int bits) {
     if (bits != 32 && (bits < 2 || bits > 16))
-        return dense_error(DQRM_E_INVALID, "dqrm_dense: bits must be 2..16 or 32 (got %d)", bits);
+        return set_error(DQRM_E_INVALID, "dqrm_dense: bits must be 2..16 or 32 (got %d)", bits);
     return DQRM_OK;
 }
 
@@ -200,12 +171,12 @@ int dqrm_dense_grad_scale(const dqrm_dense_set* set, int bits, float* s_loc, voi
     int rc = check_dense(set);
     if (rc) return rc;
     if ((rc = check_bits(bits))) return rc;
-    if (bits == 32) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_scale: no scale for unquantized gradients");
+    if (bits == 32) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_scale: no scale for unquantized gradients");
     if (set->num_channels == 0) return DQRM_OK;
-    if (!s_loc) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_scale: null s_loc");
+    if (!s_loc) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_scale: null s_loc");
     const float qmax = (float)((1 << (bits - 1)) - 1);
     hipLaunchKernelGGL(k_dense_scale, grid_of(set), dim3(DWG), 0, (hipStream_t)stream, args_of(set), qmax, s_loc);
-    DHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -214,17 +185,17 @@ int dqrm_dense_grad_quant(const dqrm_dense_set* set, int bits, const float* s_al
     int rc = check_dense(set);
     if (rc) return rc;
     if ((rc = check_bits(bits))) return rc;
-    if (num_ranks < 1) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: num_ranks < 1");
+    if (num_ranks < 1) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: num_ranks < 1");
     if (set->num_channels == 0) return DQRM_OK;
-    if (!wire) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: null wire");
+    if (!wire) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: null wire");
     if ((bits == 32) != (wire_type == DQRM_WIRE_F32))
-        return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: wire type %d does not match bits %d", wire_type, bits);
+        return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: wire type %d does not match bits %d", wire_type, bits);
     if (bits != 32) {
-        if (!s_all || !s_avg) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: null scale buffers");
+        if (!s_all || !s_avg) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: null scale buffers");
         const int need = dqrm_dense_wire_type(bits, num_ranks);
         if (wire_type == DQRM_WIRE_F16 && need != DQRM_WIRE_F16)
-            return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: fp16 wire inexact for bits %d, %d ranks",
-                               bits, num_ranks);
+            return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: fp16 wire inexact for bits %d, %d ranks",
+                             bits, num_ranks);
     }
     const float inv_n = 1.0f / (float)num_ranks;
     const int n = bits == 32 ? 0 : (1 << (bits - 1)) - 1;
@@ -244,18 +215,18 @@ int dqrm_dense_grad_quant(const dqrm_dense_set* set, int bits, const float* s_al
                                num_ranks, inv_n, lo, hi, s_avg, (float*)wire);
             break;
         default:
-            return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: unknown wire type %d", wire_type);
+            return set_error(DQRM_E_INVALID, "dqrm_dense_grad_quant: unknown wire type %d", wire_type);
     }
-    DHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
 int dqrm_dense_grad_decode(const dqrm_dense_set* set, const void* wire, int wire_type, int num_ranks, void* stream) {
     int rc = check_dense(set);
     if (rc) return rc;
-    if (num_ranks < 1) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: num_ranks < 1");
+    if (num_ranks < 1) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: num_ranks < 1");
     if (set->num_channels == 0) return DQRM_OK;
-    if (!wire) return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: null wire");
+    if (!wire) return set_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: null wire");
     const float inv_n = 1.0f / (float)num_ranks;
     hipStream_t st = (hipStream_t)stream;
     switch (wire_type) {
@@ -272,9 +243,9 @@ int dqrm_dense_grad_decode(const dqrm_dense_set* set, const void* wire, int wire
                                (const float*)wire, inv_n);
             break;
         default:
-            return dense_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: unknown wire type %d", wire_type);
+            return set_error(DQRM_E_INVALID, "dqrm_dense_grad_decode: unknown wire type %d", wire_type);
     }
-    DHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -283,7 +254,7 @@ int dqrm_dense_update(const dqrm_dense_set* set, const float* s, float lr, void*
     if (rc) return rc;
     if (set->num_channels == 0) return DQRM_OK;
     hipLaunchKernelGGL(k_dense_update, grid_of(set), dim3(DWG), 0, (hipStream_t)stream, args_of(set), s, -lr);
-    DHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 

@@ -1,6 +1,8 @@
 // dqrm_device.h — device helpers shared by the translation units of libdqrm (not part
-// of the C ABI): table metadata, the quantization arithmetic, write-through stores and
-// dirty flags of the |W| hierarchy, the in-launch hand-off and the table finalize.
+// of the C ABI): the quantization arithmetic every unit with a kernel that quantizes or
+// reduces a wave takes from here (WAVE, wave_max, fake_quant; no unit defines its own),
+// table metadata, write-through stores and dirty flags of the |W| hierarchy, the in-launch
+// hand-off and the table finalize.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,6 +75,9 @@ DQRM_INLINE float group_max(float v) {
     return v;
 }
 
+// The one wave reduction of every unit. Its callers reduce fabsf results or 0: over
+// non-negative values (and NaN, which fmaxf drops on either side) the maximum does not depend
+// on the order of the xor steps, so the bits are those of any other butterfly.
 DQRM_INLINE float wave_max(float v) { return group_max<WAVE>(v); }
 
 // pack 4 quantized values (ints in [-8,7] held as float) into 2 offset-binary bytes

@@ -22,13 +22,10 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
 
 namespace {
 
@@ -39,14 +36,7 @@ constexpr int SPB = 64;                       // samples per workgroup pass
 constexpr int PITCH = REC + 1;                // LDS row pitch (odd: column reads hit distinct banks)
 constexpr int TPB = 256;
 
-int input_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
+using dqrm_internal::set_error;
 
 // torch.remainder on int32 (Python semantics: the result takes the divisor's sign)
 __device__ __forceinline__ int32_t py_mod(int32_t x, int32_t m) {
@@ -88,17 +78,15 @@ extern "C" {
 
 int dqrm_criteo_unpack(const int32_t* records, int64_t num_samples, int32_t max_ind_range, float* dense,
                        int64_t* lS_i, float* labels, int64_t* lS_o, void* stream) {
-    if (num_samples < 0) return input_error(DQRM_E_INVALID, "dqrm_criteo_unpack: negative sample count");
+    if (num_samples < 0) return set_error(DQRM_E_INVALID, "dqrm_criteo_unpack: negative sample count");
     if (num_samples == 0) return DQRM_OK;
     if (!records || !dense || !lS_i || !labels)
-        return input_error(DQRM_E_INVALID, "dqrm_criteo_unpack: null pointer");
+        return set_error(DQRM_E_INVALID, "dqrm_criteo_unpack: null pointer");
     int64_t blocks = (num_samples + SPB - 1) / SPB;
     if (blocks > 8192) blocks = 8192;  // grid-stride beyond (~32 workgroups per CU)
     hipLaunchKernelGGL(k_criteo_unpack, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, records,
                        num_samples, max_ind_range, dense, lS_i, labels, lS_o);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return input_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e), (int)e);
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 

@@ -35,17 +35,16 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int IWG = 256;             // threads per workgroup (one sample)
 constexpr int SWG = 256;             // abs-max: threads per workgroup
 constexpr int kScaleMaxGrid = 512;   // abs-max: workgroups at most (grid-stride beyond)
@@ -55,22 +54,6 @@ constexpr int kMaxD = 256;
 constexpr size_t kPlainLds = 64 * 1024;  // dynamic LDS a launch may ask for without raising the kernel's limit
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-int interact_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define IHIP_TRY(expr)                                                                           \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return interact_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
 
 struct IArgs {
     int F, D, self, quant, P;
@@ -85,18 +68,6 @@ struct IArgs {
     float* dx;           // bwd: [B][D], nullable
     float* demb;         // bwd: [B][F-1][D], nullable
 };
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-// torch.round (half to even) == rintf; clamp to [lo, hi]
-__device__ __forceinline__ float quant1(float v, float rcp, float lo, float hi) {
-    const float q = rintf(rcp * v + 0.0f);
-    return fminf(fmaxf(q, lo), hi);
-}
 
 // first pair index of row i in the reference's li / lj order:
 // for i in range(F): for j in range(i + (1 if itself else 0))
@@ -129,10 +100,10 @@ __device__ __forceinline__ void stage_tile(const IArgs& a, int64_t b, float* til
             pass[4 * q + 3] = v.w;
         }
         if (a.quant) {
-            v.x = quant1(v.x, rcp, a.lo, a.hi);
-            v.y = quant1(v.y, rcp, a.lo, a.hi);
-            v.z = quant1(v.z, rcp, a.lo, a.hi);
-            v.w = quant1(v.w, rcp, a.lo, a.hi);
+            v.x = fake_quant(v.x, rcp, a.lo, a.hi);
+            v.y = fake_quant(v.y, rcp, a.lo, a.hi);
+            v.z = fake_quant(v.z, rcp, a.lo, a.hi);
+            v.w = fake_quant(v.w, rcp, a.lo, a.hi);
         }
         *reinterpret_cast<f32x4*>(tile + f * LD + 4 * q) = v;
     }
@@ -273,47 +244,47 @@ int64_t num_pairs(int F, int self) { return (int64_t)F * (F - 1) / 2 + (self ? F
 bool misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
 int check_interact(const dqrm_interact* c, const char* what) {
-    if (!c) return interact_error(DQRM_E_INVALID, "%s: null interaction config", what);
+    if (!c) return set_error(DQRM_E_INVALID, "%s: null interaction config", what);
     if (c->num_features < 2 || c->num_features > kMaxF)
-        return interact_error(DQRM_E_INVALID, "%s: num_features must be 2..%d (got %d)", what, kMaxF,
-                              c->num_features);
+        return set_error(DQRM_E_INVALID, "%s: num_features must be 2..%d (got %d)", what, kMaxF,
+                         c->num_features);
     if (c->dim < 4 || c->dim > kMaxD || c->dim % 4 != 0)
-        return interact_error(DQRM_E_INVALID, "%s: dim must be a multiple of 4 in 4..%d (got %d)", what, kMaxD,
-                              c->dim);
+        return set_error(DQRM_E_INVALID, "%s: dim must be a multiple of 4 in 4..%d (got %d)", what, kMaxD,
+                         c->dim);
     if (c->quant_bits != 0 && (c->quant_bits < 2 || c->quant_bits > 16))
-        return interact_error(DQRM_E_INVALID, "%s: quant_bits must be 0 or 2..16 (got %d)", what, c->quant_bits);
+        return set_error(DQRM_E_INVALID, "%s: quant_bits must be 0 or 2..16 (got %d)", what, c->quant_bits);
     if (c->emb_stride_b < 0 || c->emb_stride_b % 4 != 0)
-        return interact_error(DQRM_E_INVALID, "%s: emb_stride_b must be a non-negative multiple of 4 (got %lld)",
-                              what, (long long)c->emb_stride_b);
+        return set_error(DQRM_E_INVALID, "%s: emb_stride_b must be a non-negative multiple of 4 (got %lld)",
+                         what, (long long)c->emb_stride_b);
     if (c->emb_stride_f < 0 || c->emb_stride_f % 4 != 0)
-        return interact_error(DQRM_E_INVALID, "%s: emb_stride_f must be a non-negative multiple of 4 (got %lld)",
-                              what, (long long)c->emb_stride_f);
+        return set_error(DQRM_E_INVALID, "%s: emb_stride_f must be a non-negative multiple of 4 (got %lld)",
+                         what, (long long)c->emb_stride_f);
     return DQRM_OK;
 }
 
 // B: 0 <= B and B * F * D / 4 within 32 bits (the abs-max kernel's piece index)
 int check_batch(const dqrm_interact* c, int64_t B, const char* what) {
-    if (B < 0) return interact_error(DQRM_E_INVALID, "%s: B must be >= 0 (got %lld)", what, (long long)B);
+    if (B < 0) return set_error(DQRM_E_INVALID, "%s: B must be >= 0 (got %lld)", what, (long long)B);
     if (B > (int64_t)INT32_MAX / ((int64_t)c->num_features * (c->dim / 4)))
-        return interact_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
-                              (long long)B);
+        return set_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
+                         (long long)B);
     return DQRM_OK;
 }
 
 int check_scale_arg(const dqrm_interact* c, const float* scale, const char* what) {
     if (c->quant_bits != 0 && !scale)
-        return interact_error(DQRM_E_INVALID, "%s: quant_bits = %d needs a scale (got NULL)", what, c->quant_bits);
+        return set_error(DQRM_E_INVALID, "%s: quant_bits = %d needs a scale (got NULL)", what, c->quant_bits);
     if (c->quant_bits == 0 && scale)
-        return interact_error(DQRM_E_INVALID, "%s: scale must be NULL when quant_bits is 0", what);
+        return set_error(DQRM_E_INVALID, "%s: scale must be NULL when quant_bits is 0", what);
     if (scale && ((uintptr_t)scale & 3u))
-        return interact_error(DQRM_E_INVALID, "%s: scale is not 4-byte aligned", what);
+        return set_error(DQRM_E_INVALID, "%s: scale is not 4-byte aligned", what);
     return DQRM_OK;
 }
 
 #define ICHECK_PTR(p, name)                                                                   \
     do {                                                                                      \
-        if (!(p)) return interact_error(DQRM_E_INVALID, "%s: null %s", what, name);           \
-        if (misaligned(p)) return interact_error(DQRM_E_INVALID, "%s: %s is not 16-byte aligned", what, name); \
+        if (!(p)) return set_error(DQRM_E_INVALID, "%s: null %s", what, name);           \
+        if (misaligned(p)) return set_error(DQRM_E_INVALID, "%s: %s is not 16-byte aligned", what, name); \
     } while (0)
 
 IArgs make_args(const dqrm_interact* c, const float* x, const float* emb, int64_t B, const float* scale) {
@@ -341,10 +312,10 @@ IArgs make_args(const dqrm_interact* c, const float* x, const float* emb, int64_
 template <typename K>
 int launch_samples(K kernel, const IArgs& a, size_t lds, hipStream_t st) {
     if (lds > kPlainLds)  // F = 64 with D near 256: the tile is past 64 KiB
-        IHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DQRM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kernel, dim3((unsigned)a.B), dim3(IWG), lds, st, a);
-    IHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -366,7 +337,7 @@ int dqrm_interact_scale(const dqrm_interact* cfg, const float* x, const float* e
     int rc = check_interact(cfg, what);
     if (rc) return rc;
     if (cfg->quant_bits == 0)
-        return interact_error(DQRM_E_INVALID, "%s: quant_bits is 0 (the plain interaction has no scale)", what);
+        return set_error(DQRM_E_INVALID, "%s: quant_bits is 0 (the plain interaction has no scale)", what);
     if ((rc = check_batch(cfg, B, what))) return rc;
     if ((rc = check_scale_arg(cfg, scale, what))) return rc;
     if (B == 0) return DQRM_OK;
@@ -377,9 +348,9 @@ int dqrm_interact_scale(const dqrm_interact* cfg, const float* x, const float* e
     const int64_t want = ((int64_t)total4 + SWG * 4 - 1) / (SWG * 4);
     const unsigned grid = (unsigned)(want < kScaleMaxGrid ? want : kScaleMaxGrid);
     hipStream_t st = (hipStream_t)stream;
-    IHIP_TRY(hipMemsetAsync(scale, 0, sizeof(float), st));  // below every clamp(m, 1e-8) / n
+    DQRM_HIP_TRY(hipMemsetAsync(scale, 0, sizeof(float), st));  // below every clamp(m, 1e-8) / n
     hipLaunchKernelGGL(k_interact_absmax, dim3(grid), dim3(SWG), 0, st, a, a.hi, total4, scale);
-    IHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -411,8 +382,8 @@ int dqrm_interact_bwd(const dqrm_interact* cfg, const float* x, const float* emb
     ICHECK_PTR(x, "x");
     ICHECK_PTR(emb, "emb");
     ICHECK_PTR(dr, "dr");
-    if (dx && misaligned(dx)) return interact_error(DQRM_E_INVALID, "%s: dx is not 16-byte aligned", what);
-    if (demb && misaligned(demb)) return interact_error(DQRM_E_INVALID, "%s: demb is not 16-byte aligned", what);
+    if (dx && misaligned(dx)) return set_error(DQRM_E_INVALID, "%s: dx is not 16-byte aligned", what);
+    if (demb && misaligned(demb)) return set_error(DQRM_E_INVALID, "%s: demb is not 16-byte aligned", what);
     if (!dx && !demb) return DQRM_OK;  // nothing asked for
     IArgs a = make_args(cfg, x, emb, B, scale);
     a.dr = dr;

@@ -1,5 +1,6 @@
-// dqrm_internal.h — launch interface between the translation units of libdqrm (not part of
-// the C ABI; include/dqrm.h is).
+// dqrm_internal.h — what the translation units of libdqrm share on the host (not part of the
+// C ABI; include/dqrm.h is): the error path, the validation one unit does for another, and the
+// launch interface between units. A new unit includes this and defines no copy of any of it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,41 @@
 #include "../../include/dqrm.h"
 
 namespace dqrm_internal {
+
+#define DQRM_HIDDEN __attribute__((visibility("hidden")))
+
+// The one error path: formats into the calling thread's dqrm_last_error() text and returns
+// `code` (dqrm_kernels.hip).
+DQRM_HIDDEN __attribute__((format(printf, 2, 3))) int set_error(int code, const char* fmt, ...);
+
+#define DQRM_HIP_TRY(expr)                                                                                      \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess)                                                                                   \
+            return dqrm_internal::set_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
+    } while (0)
+
+// dqrm_linear.hip: what every dqrm_linear_* export rejects in a layer (quantized: the integer
+// buffers and bit widths as well) and in an activation code. Texts are "<who>: <fault>".
+DQRM_HIDDEN int check_linear(const dqrm_linear* l, int quantized, const char* who);
+DQRM_HIDDEN int check_act(int act, const char* who);
+
+// dqrm_mlp.hip: a stack as dqrm_mlp_fwd rejects it, and whether one of its layers quantizes per
+// tensor (the fused SGD + requantize then takes a second launch and a workspace).
+DQRM_HIDDEN int check_mlp(const dqrm_mlp* m, const char* who);
+DQRM_HIDDEN bool has_tensor_layer(const dqrm_mlp* m);
+
+// dqrm_kernels.hip, for the whole-model step (dqrm_model.hip), which validates its embedding
+// stage before its first launch: everything dqrm_emb_fwd and dqrm_emb_bwd_sgd / _sgd_fwd reject,
+// apart from the out / dy pointers and strides, which that caller lays out itself. batch == NULL:
+// the set alone. training == 0: the forward's checks only. next: the batch whose forward follows
+// the update (nullable).
+DQRM_HIDDEN int emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, int bits,
+                          uint32_t fwd_flags, int repack_bits, int training, const char* who);
+// launches of dqrm_emb_bwd_sgd (next == NULL) / dqrm_emb_bwd_sgd_fwd on arguments that passed
+// emb_check
+DQRM_HIDDEN int emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
+                                     uint32_t fwd_flags);
 
 // The coalesce backward of a Criteo-form batch (DQRM_BATCH_POOLING_ONE: table t's lookups
 // are idx[t*B, (t+1)*B), bag b = lookup b), written into the caller's coalesced-gradient

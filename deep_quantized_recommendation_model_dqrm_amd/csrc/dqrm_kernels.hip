@@ -59,7 +59,9 @@ __device__ unsigned long long g_diag_clk[8192 * 16];
 // ------------------------------------------------------------------------------------
 thread_local char g_last_error[512] = "";
 
-int set_error(int code, const char* fmt, ...) {
+}  // namespace
+
+int dqrm_internal::set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
@@ -67,14 +69,11 @@ int set_error(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return set_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_);                                           \
-    } while (0)
+namespace {
 
-#define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
+using dqrm_internal::set_error;
+
+#define LAUNCH_CHECK() DQRM_HIP_TRY(hipGetLastError())
 
 constexpr int MAX_TABLES = 256;
 constexpr int DQRM_MAX_RANKS = 64;    // dqrm_apply_sparse_update: num_ranks <= 64
@@ -4155,7 +4154,7 @@ int allow_lds(K kernel, size_t bytes) {
     const void* f = reinterpret_cast<const void*>(kernel);
     for (int i = 0; i < nseen; ++i)
         if (seen[i] == f && seen_bytes[i] >= bytes) return DQRM_OK;
-    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    DQRM_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     if (nseen < 64) { seen[nseen] = f; seen_bytes[nseen] = bytes; ++nseen; }
     return DQRM_OK;
 }
@@ -4350,18 +4349,14 @@ extern "C" {
 
 #ifdef DQRM_DIAG_CLOCK
 int dqrm_diag_clock_read(unsigned long long* host, int n) {
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_diag_clk), (size_t)n * sizeof(unsigned long long)));
+    DQRM_HIP_TRY(hipDeviceSynchronize());
+    DQRM_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_diag_clk), (size_t)n * sizeof(unsigned long long)));
     return DQRM_OK;
 }
 #endif
 
 const char* dqrm_last_error(void) { return g_last_error; }
 
-// other translation units of libdqrm (dqrm_dense.hip) report through the same slot
-__attribute__((visibility("hidden"))) int dqrm_internal_set_error(int code, const char* msg) {
-    return set_error(code, "%s", msg);
-}
 int dqrm_set_coalesce_kernel(int kind) {
     if (kind != DQRM_COALESCE_AUTO && kind != DQRM_COALESCE_GENERAL)
         return set_error(DQRM_E_INVALID, "dqrm_set_coalesce_kernel: unknown kind %d", kind);
@@ -4406,9 +4401,9 @@ int dqrm_refresh_absmax(const dqrm_table_set* set, void* stream) {
     hipLaunchKernelGGL(k_level_max, dim3(grid_for(set->total_sblocks * WAVE, 256, 8192)), dim3(256), 0, st,
                        set->blkmax, set->sblkmax, set->meta, set->num_tables, 2, set->total_sblocks);
     LAUNCH_CHECK();
-    HIP_TRY(hipMemsetAsync(set->sdirty, 0, (size_t)set->total_sblocks, st));
-    HIP_TRY(hipMemsetAsync(set->bdirty, 0, (size_t)set->total_blocks, st));
-    HIP_TRY(hipMemsetAsync(set->sync, 0, (size_t)set->num_tables * DQRM_SYNC_STRIDE * sizeof(uint32_t), st));
+    DQRM_HIP_TRY(hipMemsetAsync(set->sdirty, 0, (size_t)set->total_sblocks, st));
+    DQRM_HIP_TRY(hipMemsetAsync(set->bdirty, 0, (size_t)set->total_blocks, st));
+    DQRM_HIP_TRY(hipMemsetAsync(set->sync, 0, (size_t)set->num_tables * DQRM_SYNC_STRIDE * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_table_max, dim3(set->num_tables), dim3(256), 0, st, set->sblkmax, set->tmax,
                        set->meta, set->num_tables);
     LAUNCH_CHECK();
@@ -4740,7 +4735,7 @@ int dqrm_grad_quant_pack_strided(int num_tables, int dim, const int64_t* ws_cap_
         dqrm_internal::QuantPackArgs q{num_tables, dim, ws_cap_base, ws_rows, ws_vals, ws_ucount, absmax_all,
                                        absmax_pitch, num_ranks, grad_bits, cap_base, cap_total, s_avg,
                                        (unsigned char*)payload};
-        HIP_TRY(dqrm_internal::launch_quant_pack(q, st));
+        DQRM_HIP_TRY(dqrm_internal::launch_quant_pack(q, st));
         return DQRM_OK;
     }
     DISPATCH_LPR(dim, {
@@ -5068,7 +5063,7 @@ static int apply_update_ex(const dqrm_table_set* set, const int64_t* cap_base, i
             r.fwd_scale = set->scale; r.fwd_bits = nf->bits; r.fwd_flags = nf->flags;
             r.fwd_gx = dqrm_internal::merge_forward_gx(nf->B); r.spin_limit = spin;
         }
-        HIP_TRY(dqrm_internal::launch_apply_merge(r, st));
+        DQRM_HIP_TRY(dqrm_internal::launch_apply_merge(r, st));
         return DQRM_OK;  // the |W| hierarchy is finalized inside the launch
     }
     if (nf) return set_error(DQRM_E_INVALID, "%s: a fused forward needs the merge kernel", "dqrm_apply_sparse_update");
@@ -5082,7 +5077,7 @@ static int apply_update_ex(const dqrm_table_set* set, const int64_t* cap_base, i
                                         a.sync, a.pscale, a.meta, a.err, cap_base, cap_total, a.payloads,
                                         (int64_t)rank_pitch, num_ranks, a.T, D, grad_bits, s_avg, -lr, mode,
                                         a.repack, (int)K};
-        HIP_TRY(dqrm_internal::launch_apply_ranges(r, st));
+        DQRM_HIP_TRY(dqrm_internal::launch_apply_ranges(r, st));
         return DQRM_OK;  // the |W| hierarchy is finalized inside the launch
     }
     // AUTO: flat while each lane of a row's group searches at most one other rank
@@ -5272,13 +5267,10 @@ int dqrm_bwd_sgd_fwd_is_one_launch(const dqrm_table_set* set, const dqrm_batch* 
     return sgd_small_plan(set, batch, next, fwd_flags, nullptr) == 2 ? 1 : 0;
 }
 
-// The whole-model step (dqrm_model.hip) validates its embedding stage before its first launch:
-// everything dqrm_emb_fwd and dqrm_emb_bwd_sgd / _sgd_fwd reject, apart from the out / dy pointers
-// and strides, which that caller lays out itself. batch == NULL: the set alone. training == 0:
-// the forward's checks only. next: the batch whose forward follows the update (nullable).
-__attribute__((visibility("hidden"))) int dqrm_internal_emb_check(const dqrm_table_set* set, const dqrm_batch* batch,
-                                                                  const dqrm_batch* next, int bits, uint32_t fwd_flags,
-                                                                  int repack_bits, int training, const char* who) {
+}  // extern "C"
+
+int dqrm_internal::emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, int bits,
+                             uint32_t fwd_flags, int repack_bits, int training, const char* who) {
     int rc = check_set(set);
     if (rc) return rc;
     if (!(fwd_flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
@@ -5297,12 +5289,8 @@ __attribute__((visibility("hidden"))) int dqrm_internal_emb_check(const dqrm_tab
     return DQRM_OK;
 }
 
-// launches of dqrm_emb_bwd_sgd (next == NULL) / dqrm_emb_bwd_sgd_fwd on arguments that passed
-// dqrm_internal_emb_check
-__attribute__((visibility("hidden"))) int dqrm_internal_emb_bwd_sgd_launches(const dqrm_table_set* set,
-                                                                             const dqrm_batch* batch,
-                                                                             const dqrm_batch* next,
-                                                                             uint32_t fwd_flags) {
+int dqrm_internal::emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
+                                        uint32_t fwd_flags) {
     const int fwd = next && next->num_bags > 0 ? 1 : 0;
     if (batch->num_bags <= 0) return fwd;
     const int plan = sgd_small_plan(set, batch, next, fwd_flags, nullptr);
@@ -5310,6 +5298,8 @@ __attribute__((visibility("hidden"))) int dqrm_internal_emb_bwd_sgd_launches(con
     if (plan == 1) return 1 + fwd;
     return 1 + finalize_launch() + fwd;
 }
+
+extern "C" {
 
 static int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
                            int64_t dy_stride_b, int ste, const int64_t* ws_cap_base, int64_t ws_cap_total,
@@ -5369,9 +5359,9 @@ static int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, c
 int dqrm_read_errors(const dqrm_table_set* set, uint32_t* flags, int clear, void* stream) {
     if (!set || !set->err || !flags) return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_read_errors");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(flags, set->err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (clear) HIP_TRY(hipMemsetAsync(set->err, 0, sizeof(uint32_t), st));
+    DQRM_HIP_TRY(hipMemcpyAsync(flags, set->err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DQRM_HIP_TRY(hipStreamSynchronize(st));
+    if (clear) DQRM_HIP_TRY(hipMemsetAsync(set->err, 0, sizeof(uint32_t), st));
     return DQRM_OK;
 }
 

@@ -36,51 +36,22 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int LWG = 256;            // threads per workgroup (4 waves, 2 x 2)
 constexpr int QWG = 256;            // wquant: threads per workgroup
 constexpr int QRPW = QWG / WAVE;    // wquant: weight rows per workgroup (one per wave)
 constexpr int AWG = 1024;           // per-tensor abs-max: one workgroup
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-int linear_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define LHIP_TRY(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return linear_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-// torch.round (half to even) == rintf; clamp to [lo, hi]
-__device__ __forceinline__ float quant1(float w, float rcp, float lo, float hi) {
-    const float q = rintf(rcp * w + 0.0f);
-    return fminf(fmaxf(q, lo), hi);
-}
 
 // ------------------------------------------------------------------------------ wquant
 struct QuantArgs {
@@ -104,9 +75,9 @@ __device__ __forceinline__ void quant_bias(const QuantArgs& a, int o, float s, f
     if (QA) {
         const float c = s * a.prev[0];
         if (cos_at >= 0) a.cos[cos_at] = c;
-        a.bi[o] = quant1(a.b[o], 1.0f / c, a.blo, a.bhi);
+        a.bi[o] = fake_quant(a.b[o], 1.0f / c, a.blo, a.bhi);
     } else {
-        a.bi[o] = quant1(a.b[o], rcp, a.blo, a.bhi);
+        a.bi[o] = fake_quant(a.b[o], rcp, a.blo, a.bhi);
     }
 }
 
@@ -123,7 +94,7 @@ __global__ void __launch_bounds__(QWG) k_wquant_rows(QuantArgs a) {
     m = wave_max(m);
     const float s = fmaxf(m, 1e-8f) / a.n;
     const float rcp = 1.0f / s;
-    for (int k = lane; k < a.in; k += WAVE) wi[k] = quant1(w[k], rcp, a.wlo, a.whi);
+    for (int k = lane; k < a.in; k += WAVE) wi[k] = fake_quant(w[k], rcp, a.wlo, a.whi);
     if (lane == 0) {
         a.scale[o] = s;
         quant_bias<QA>(a, o, s, rcp, o);
@@ -156,7 +127,7 @@ __global__ void __launch_bounds__(QWG) k_wquant_tensor(QuantArgs a) {
     float* __restrict__ wi = a.wi + (int64_t)o * a.in;
     const float s = a.scale[0];
     const float rcp = 1.0f / s;
-    for (int k = lane; k < a.in; k += WAVE) wi[k] = quant1(w[k], rcp, a.wlo, a.whi);
+    for (int k = lane; k < a.in; k += WAVE) wi[k] = fake_quant(w[k], rcp, a.wlo, a.whi);
     if (lane == 0) quant_bias<QA>(a, o, s, rcp, o == 0 ? 0 : -1);
 }
 
@@ -367,14 +338,14 @@ template <int MODE, int ACT, bool QA>
 int launch_gemm_act(const GemmArgs& g, hipStream_t st, const char* what) {
     const int64_t bm = (g.M + 31) / 32, bn = (g.N + 31) / 32;
     if (bm * bn < kSmallTileMax) {
-        if (bm > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
+        if (bm > 65535) return set_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
         hipLaunchKernelGGL((k_linear_gemm<1, MODE, ACT, QA>), dim3((unsigned)bn, (unsigned)bm), dim3(LWG), 0, st, g);
     } else {
         const int64_t bm2 = (g.M + 63) / 64, bn2 = (g.N + 63) / 64;
-        if (bm2 > 65535) return linear_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
+        if (bm2 > 65535) return set_error(DQRM_E_CAPACITY, "%s: more than 65535 row tiles", what);
         hipLaunchKernelGGL((k_linear_gemm<2, MODE, ACT, QA>), dim3((unsigned)bn2, (unsigned)bm2), dim3(LWG), 0, st, g);
     }
-    LHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -387,31 +358,38 @@ int launch_gemm(const GemmArgs& g, int act, hipStream_t st, const char* what) {
     }
 }
 
-int check_act(int act, const char* what) {
+}  // namespace
+
+int dqrm_internal::check_act(int act, const char* what) {
     if (act < DQRM_ACT_NONE || act > DQRM_ACT_SIGMOID)
-        return linear_error(DQRM_E_INVALID, "%s: act must be DQRM_ACT_NONE, _RELU or _SIGMOID (got %d)", what, act);
+        return set_error(DQRM_E_INVALID, "%s: act must be DQRM_ACT_NONE, _RELU or _SIGMOID (got %d)", what, act);
     return DQRM_OK;
 }
 
-int check_linear(const dqrm_linear* l, int quantized, const char* what) {
-    if (!l) return linear_error(DQRM_E_INVALID, "%s: null layer", what);
+int dqrm_internal::check_linear(const dqrm_linear* l, int quantized, const char* what) {
+    if (!l) return set_error(DQRM_E_INVALID, "%s: null layer", what);
     if (l->in_features < 1 || l->out_features < 1)
-        return linear_error(DQRM_E_INVALID, "%s: in_features / out_features must be positive (got %d / %d)", what,
-                            l->in_features, l->out_features);
-    if (!l->weight || !l->bias) return linear_error(DQRM_E_INVALID, "%s: null weight / bias", what);
+        return set_error(DQRM_E_INVALID, "%s: in_features / out_features must be positive (got %d / %d)", what,
+                         l->in_features, l->out_features);
+    if (!l->weight || !l->bias) return set_error(DQRM_E_INVALID, "%s: null weight / bias", what);
     if (quantized) {
         if (l->weight_bit < 2 || l->weight_bit > 32 || l->bias_bit < 2 || l->bias_bit > 32)
-            return linear_error(DQRM_E_INVALID, "%s: weight_bit / bias_bit must be 2..32 (got %d / %d)", what,
-                                l->weight_bit, l->bias_bit);
+            return set_error(DQRM_E_INVALID, "%s: weight_bit / bias_bit must be 2..32 (got %d / %d)", what,
+                             l->weight_bit, l->bias_bit);
         if (!l->weight_integer || !l->bias_integer || !l->scale)
-            return linear_error(DQRM_E_INVALID, "%s: null weight_integer / bias_integer / scale", what);
+            return set_error(DQRM_E_INVALID, "%s: null weight_integer / bias_integer / scale", what);
     }
     return DQRM_OK;
 }
 
+namespace {
+
+using dqrm_internal::check_act;
+using dqrm_internal::check_linear;
+
 // the integer-activation calls: one-float prev and the [O] / [1] out_scale
 int check_qact(const float* prev, const float* out_scale, const char* what) {
-    if (!prev || !out_scale) return linear_error(DQRM_E_INVALID, "%s: null prev / out_scale", what);
+    if (!prev || !out_scale) return set_error(DQRM_E_INVALID, "%s: null prev / out_scale", what);
     return DQRM_OK;
 }
 
@@ -431,10 +409,10 @@ int linear_wquant(const dqrm_linear* l, const float* prev, float* out_scale, voi
         hipLaunchKernelGGL(k_wquant_rows<QA>, grid, dim3(QWG), 0, st, a);
     } else {
         hipLaunchKernelGGL(k_wquant_absmax, dim3(1), dim3(AWG), 0, st, a);
-        LHIP_TRY(hipGetLastError());
+        DQRM_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_wquant_tensor<QA>, grid, dim3(QWG), 0, st, a);
     }
-    LHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
@@ -447,9 +425,9 @@ int linear_fwd(const dqrm_linear* l, int quantized, int act, const float* x, con
     if (rc) return rc;
     if ((rc = check_act(act, what))) return rc;
     if (QA && (rc = check_qact(prev, out_scale, what))) return rc;
-    if (B < 0 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (B < 0 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
     if (B == 0) return DQRM_OK;
-    if (!x || !y) return linear_error(DQRM_E_INVALID, "%s: null x / y", what);
+    if (!x || !y) return set_error(DQRM_E_INVALID, "%s: null x / y", what);
     GemmArgs g{};
     g.M = (int)B;
     g.N = l->out_features;
@@ -472,10 +450,10 @@ int linear_bwd(const dqrm_linear* l, int quantized, int act, const float* x, con
     if (rc) return rc;
     if ((rc = check_act(act, what))) return rc;
     if (QA && (rc = check_qact(prev, out_scale, what))) return rc;
-    if (B < 1 || B > INT32_MAX) return linear_error(DQRM_E_INVALID, "%s: bad batch size", what);
-    if (!x || !dy || !dw || !db) return linear_error(DQRM_E_INVALID, "%s: null x / dy / dw / db", what);
+    if (B < 1 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!x || !dy || !dw || !db) return set_error(DQRM_E_INVALID, "%s: null x / dy / dw / db", what);
     if (act != DQRM_ACT_NONE && !y)
-        return linear_error(DQRM_E_INVALID, "%s: an activation's backward needs the forward's output (null y)", what);
+        return set_error(DQRM_E_INVALID, "%s: an activation's backward needs the forward's output (null y)", what);
     hipStream_t st = (hipStream_t)stream;
     GemmArgs g{};
     g.Y = act != DQRM_ACT_NONE ? y : nullptr;

@@ -20,7 +20,6 @@
 // row's first lookup sums the row's dy slices along its ordered list, PS_RUN loads in flight.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "dqrm_device.h"
 #include "dqrm_internal.h"
@@ -215,17 +214,11 @@ hipError_t launch_lookup_grad_presum(const PresumArgs& a, hipStream_t stream) {
 
 }  // namespace dqrm_internal
 
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
-
 extern "C" int dqrm_emb_bwd_lookup_grad_presum(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
                                                int64_t dy_stride_t, int64_t dy_stride_b, int ste, int64_t* rows,
                                                float* vals, void* stream) {
     const char* who = "dqrm_emb_bwd_lookup_grad_presum";
-    char buf[256];
-    auto err = [&](int code, const char* what) {
-        snprintf(buf, sizeof(buf), "%s: %s", who, what);
-        return dqrm_internal_set_error(code, buf);
-    };
+    auto err = [&](int code, const char* what) { return dqrm_internal::set_error(code, "%s: %s", who, what); };
     if (!set || !batch || !set->meta || !set->scale || !set->err || set->num_tables <= 0)
         return err(DQRM_E_INVALID, "null table set / batch");
     const int D = set->dim;

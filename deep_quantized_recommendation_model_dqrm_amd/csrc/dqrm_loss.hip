@@ -31,38 +31,21 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int kSlots = 256;                   // the forward's one workgroup: a thread per slot
 constexpr int64_t kMaxB = (int64_t)1 << 20;   // largest batch of the one-workgroup forward
 constexpr int kBatch = 8;                     // elements a thread loads before it computes them
 constexpr int EWG = 256;                      // backward: threads per workgroup
 constexpr int kMaxElemGroups = 1 << 12;       // backward grid cap (kMaxB / EWG: never grid-strides)
-
-int loss_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define LHIP_TRY(expr)                                                                         \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return loss_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
 
 // max(v, floor) that keeps a NaN v (fmaxf would return the floor)
 __device__ __forceinline__ float floor_at(float v, float floor) { return v < floor ? floor : v; }
@@ -165,15 +148,15 @@ extern "C" {
 int dqrm_loss_fwd(const dqrm_loss* cfg, const float* p, const float* t, int64_t B, float* loss, float* g, float* z,
                   float* terms, void* stream) {
     const char* what = "dqrm_loss_fwd";
-    if (!cfg) return loss_error(DQRM_E_INVALID, "%s: null dqrm_loss", what);
+    if (!cfg) return set_error(DQRM_E_INVALID, "%s: null dqrm_loss", what);
     if (cfg->kind != DQRM_LOSS_BCE && cfg->kind != DQRM_LOSS_MSE && cfg->kind != DQRM_LOSS_WBCE)
-        return loss_error(DQRM_E_INVALID, "%s: unknown kind %d (DQRM_LOSS_BCE / _MSE / _WBCE)", what, cfg->kind);
+        return set_error(DQRM_E_INVALID, "%s: unknown kind %d (DQRM_LOSS_BCE / _MSE / _WBCE)", what, cfg->kind);
     if (cfg->kind == DQRM_LOSS_WBCE && (!cfg->weights || cfg->num_weights < 1))
-        return loss_error(DQRM_E_INVALID, "%s: DQRM_LOSS_WBCE needs weights (num_weights >= 1, got %d)", what,
-                          cfg->num_weights);
+        return set_error(DQRM_E_INVALID, "%s: DQRM_LOSS_WBCE needs weights (num_weights >= 1, got %d)", what,
+                         cfg->num_weights);
     if (B < 1 || B > kMaxB)
-        return loss_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
-    if (!p || !t || !loss) return loss_error(DQRM_E_INVALID, "%s: null p / t / loss", what);
+        return set_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
+    if (!p || !t || !loss) return set_error(DQRM_E_INVALID, "%s: null p / t / loss", what);
     hipStream_t st = (hipStream_t)stream;
     const int clamp = cfg->clamp ? 1 : 0;
 #define LOSS_LAUNCH(KIND)                                                                                       \
@@ -186,19 +169,19 @@ int dqrm_loss_fwd(const dqrm_loss* cfg, const float* p, const float* t, int64_t 
     else
         LOSS_LAUNCH(DQRM_LOSS_BCE);
 #undef LOSS_LAUNCH
-    LHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 
 int dqrm_loss_bwd(const float* g, const float* go, int64_t B, float* dp, void* stream) {
     const char* what = "dqrm_loss_bwd";
     if (B < 1 || B > kMaxB)
-        return loss_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
-    if (!g || !go || !dp) return loss_error(DQRM_E_INVALID, "%s: null g / go / dp", what);
+        return set_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
+    if (!g || !go || !dp) return set_error(DQRM_E_INVALID, "%s: null g / go / dp", what);
     const int64_t groups = (B + EWG - 1) / EWG;
     hipLaunchKernelGGL(k_loss_bwd, dim3((unsigned)(groups > kMaxElemGroups ? kMaxElemGroups : groups)), dim3(EWG), 0,
                        (hipStream_t)stream, g, go, (int)B, dp);
-    LHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }
 

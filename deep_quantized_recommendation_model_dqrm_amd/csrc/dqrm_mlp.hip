@@ -27,46 +27,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdarg.h>
 #include <math.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);  // dqrm_kernels.hip (hidden)
+#include "dqrm_internal.h"
+#include "dqrm_device.h"
 
 namespace {
 
-constexpr int WAVE = 64;
+using dqrm_internal::set_error;
+
 constexpr int SWG = 256;            // threads per workgroup
 constexpr int SRPW = SWG / WAVE;    // weight rows per workgroup (one per wave)
-
-int mlp_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
-#define MHIP_TRY(expr)                                                                     \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return mlp_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-// dqrm_linear.hip's quant1: torch.round (half to even) == rintf; clamp to [lo, hi]
-__device__ __forceinline__ float quant1(float w, float rcp, float lo, float hi) {
-    const float q = rintf(rcp * w + 0.0f);
-    return fminf(fmaxf(q, lo), hi);
-}
 
 enum { UPDATE_ONLY = 0, REQUANT_ROWS = 1, REQUANT_TENSOR = 2 };
 
@@ -140,10 +112,10 @@ __global__ void __launch_bounds__(SWG) k_mlp_sgd(SgdArgs a) {
     const float s = fmaxf(m, 1e-8f) / d.n;
     const float rcp = 1.0f / s;
     float* __restrict__ wi = d.wi + (int64_t)o * in;
-    for (int k = lane; k < in; k += WAVE) wi[k] = quant1(w[k], rcp, d.wlo, d.whi);  // the lane's own stores
+    for (int k = lane; k < in; k += WAVE) wi[k] = fake_quant(w[k], rcp, d.wlo, d.whi);  // the lane's own stores
     if (lane == 0) {
         d.scale[o] = s;
-        d.bi[o] = quant1(bv, rcp, d.blo, d.bhi);
+        d.bi[o] = fake_quant(bv, rcp, d.blo, d.bhi);
     }
 }
 
@@ -163,55 +135,59 @@ __global__ void __launch_bounds__(SWG) k_mlp_requant_tensor(SgdArgs a) {
     const float rcp = 1.0f / s;
     const float* __restrict__ w = d.W + (int64_t)o * in;
     float* __restrict__ wi = d.wi + (int64_t)o * in;
-    for (int k = lane; k < in; k += WAVE) wi[k] = quant1(w[k], rcp, d.wlo, d.whi);
+    for (int k = lane; k < in; k += WAVE) wi[k] = fake_quant(w[k], rcp, d.wlo, d.whi);
     if (lane == 0) {
-        d.bi[o] = quant1(d.b[o], rcp, d.blo, d.bhi);
+        d.bi[o] = fake_quant(d.b[o], rcp, d.blo, d.bhi);
         if (o == 0) d.scale[0] = s;
     }
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------ validation
-// dqrm_linear.hip's check_linear, per layer, and the stack's own fields
-int check_stack(const dqrm_mlp* m, const char* what) {
-    if (!m) return mlp_error(DQRM_E_INVALID, "%s: null stack", what);
+// the stack's own fields, and every layer as dqrm_linear.hip checks it ("<what>: layer <i>: <fault>")
+int dqrm_internal::check_mlp(const dqrm_mlp* m, const char* what) {
+    if (!m) return set_error(DQRM_E_INVALID, "%s: null stack", what);
     if (m->num_layers < 1 || m->num_layers > DQRM_MLP_MAX_LAYERS)
-        return mlp_error(DQRM_E_INVALID, "%s: num_layers must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS,
+        return set_error(DQRM_E_INVALID, "%s: num_layers must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS,
                          m->num_layers);
     if (!m->layers || !m->quantized || !m->act)
-        return mlp_error(DQRM_E_INVALID, "%s: null layers / quantized / act array", what);
+        return set_error(DQRM_E_INVALID, "%s: null layers / quantized / act array", what);
     for (int i = 0; i < m->num_layers; ++i) {
         const dqrm_linear* l = &m->layers[i];
-        if (l->in_features < 1 || l->out_features < 1)
-            return mlp_error(DQRM_E_INVALID, "%s: layer %d: in_features / out_features must be positive (got %d / %d)",
-                             what, i, l->in_features, l->out_features);
+        char who[96];
+        snprintf(who, sizeof(who), "%s: layer %d", what, i);
+        int rc = check_linear(l, m->quantized[i], who);
+        if (rc) return rc;
         if (i > 0 && l->in_features != m->layers[i - 1].out_features)
-            return mlp_error(DQRM_E_INVALID, "%s: layer %d: in_features %d does not match layer %d's out_features %d",
-                             what, i, l->in_features, i - 1, m->layers[i - 1].out_features);
-        if (!l->weight || !l->bias) return mlp_error(DQRM_E_INVALID, "%s: layer %d: null weight / bias", what, i);
-        if (m->act[i] < DQRM_ACT_NONE || m->act[i] > DQRM_ACT_SIGMOID)
-            return mlp_error(DQRM_E_INVALID, "%s: layer %d: act must be DQRM_ACT_NONE, _RELU or _SIGMOID (got %d)",
-                             what, i, m->act[i]);
-        if (m->quantized[i]) {
-            if (l->weight_bit < 2 || l->weight_bit > 32 || l->bias_bit < 2 || l->bias_bit > 32)
-                return mlp_error(DQRM_E_INVALID, "%s: layer %d: weight_bit / bias_bit must be 2..32 (got %d / %d)",
-                                 what, i, l->weight_bit, l->bias_bit);
-            if (!l->weight_integer || !l->bias_integer || !l->scale)
-                return mlp_error(DQRM_E_INVALID, "%s: layer %d: null weight_integer / bias_integer / scale", what, i);
-        }
+            return set_error(DQRM_E_INVALID, "%s: in_features %d does not match layer %d's out_features %d", who,
+                             l->in_features, i - 1, m->layers[i - 1].out_features);
+        if ((rc = check_act(m->act[i], who))) return rc;
     }
     return DQRM_OK;
 }
 
+bool dqrm_internal::has_tensor_layer(const dqrm_mlp* m) {
+    for (int i = 0; i < m->num_layers; ++i)
+        if (m->quantized[i] && !m->layers[i].per_channel) return true;
+    return false;
+}
+
+namespace {
+
+using dqrm_internal::check_mlp;
+using dqrm_internal::has_tensor_layer;
+
 int check_flags(uint32_t flags, uint32_t known, const char* what) {
-    if (flags & ~known) return mlp_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    if (flags & ~known) return set_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
     return DQRM_OK;
 }
 
 // an array of L device pointers, none null
 int check_ptrs(const void* const* p, int L, const char* name, const char* what) {
-    if (!p) return mlp_error(DQRM_E_INVALID, "%s: null %s array", what, name);
+    if (!p) return set_error(DQRM_E_INVALID, "%s: null %s array", what, name);
     for (int i = 0; i < L; ++i)
-        if (!p[i]) return mlp_error(DQRM_E_INVALID, "%s: null %s[%d]", what, name, i);
+        if (!p[i]) return set_error(DQRM_E_INVALID, "%s: null %s[%d]", what, name, i);
     return DQRM_OK;
 }
 
@@ -220,12 +196,6 @@ int64_t max_hidden(const dqrm_mlp* m) {
     int64_t w = 0;
     for (int i = 0; i + 1 < m->num_layers; ++i) w = m->layers[i].out_features > w ? m->layers[i].out_features : w;
     return w;
-}
-
-bool has_tensor_layer(const dqrm_mlp* m) {
-    for (int i = 0; i < m->num_layers; ++i)
-        if (m->quantized[i] && !m->layers[i].per_channel) return true;
-    return false;
 }
 
 int64_t total_rows(const dqrm_mlp* m) {
@@ -264,122 +234,33 @@ void fill_layer(SgdLayer& d, const dqrm_linear* l, bool requant, const float* dw
 int launch_sgd(const SgdArgs& a, bool two, hipStream_t st) {
     const dim3 grid((unsigned)((a.total_rows + SRPW - 1) / SRPW));
     hipLaunchKernelGGL(k_mlp_sgd, grid, dim3(SWG), 0, st, a);
-    MHIP_TRY(hipGetLastError());
+    DQRM_HIP_TRY(hipGetLastError());
     if (two) {
         hipLaunchKernelGGL(k_mlp_requant_tensor, grid, dim3(SWG), 0, st, a);
-        MHIP_TRY(hipGetLastError());
+        DQRM_HIP_TRY(hipGetLastError());
     }
     return DQRM_OK;
 }
 
 // several stacks for one update launch: each a valid stack, DQRM_MLP_MAX_LAYERS layers in all
 int check_stacks(const dqrm_mlp* const* stacks, int num_stacks, const char* what) {
-    if (!stacks) return mlp_error(DQRM_E_INVALID, "%s: null stacks array", what);
+    if (!stacks) return set_error(DQRM_E_INVALID, "%s: null stacks array", what);
     if (num_stacks < 1 || num_stacks > DQRM_MLP_MAX_LAYERS)
-        return mlp_error(DQRM_E_INVALID, "%s: num_stacks must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS, num_stacks);
+        return set_error(DQRM_E_INVALID, "%s: num_stacks must be 1..%d (got %d)", what, DQRM_MLP_MAX_LAYERS, num_stacks);
     int L = 0;
     for (int s = 0; s < num_stacks; ++s) {
-        int rc = check_stack(stacks[s], what);
+        int rc = check_mlp(stacks[s], what);
         if (rc) return rc;
         L += stacks[s]->num_layers;
     }
     if (L > DQRM_MLP_MAX_LAYERS)
-        return mlp_error(DQRM_E_INVALID, "%s: the stacks have %d layers in all, at most %d fit one launch", what, L,
+        return set_error(DQRM_E_INVALID, "%s: the stacks have %d layers in all, at most %d fit one launch", what, L,
                          DQRM_MLP_MAX_LAYERS);
     return DQRM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dqrm_mlp_fwd(const dqrm_mlp* m, uint32_t flags, const float* x, int64_t B, float* const* y, void* stream) {
-    const char* what = "dqrm_mlp_fwd";
-    int rc = check_stack(m, what);
-    if (rc) return rc;
-    if ((rc = check_flags(flags, DQRM_MLP_FRESH, what))) return rc;
-    if (B < 0 || B > INT32_MAX) return mlp_error(DQRM_E_INVALID, "%s: bad batch size", what);
-    if (!y) return mlp_error(DQRM_E_INVALID, "%s: null y array", what);
-    if (B == 0) return DQRM_OK;
-    if (!x) return mlp_error(DQRM_E_INVALID, "%s: null x", what);
-    if ((rc = check_ptrs((const void* const*)y, m->num_layers, "y", what))) return rc;
-    for (int i = 0; i < m->num_layers; ++i) {
-        const dqrm_linear* l = &m->layers[i];
-        if (m->quantized[i] && !(flags & DQRM_MLP_FRESH) && (rc = dqrm_linear_wquant(l, stream))) return rc;
-        if ((rc = dqrm_linear_fwd_act(l, m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, B, y[i], stream)))
-            return rc;
-    }
-    return DQRM_OK;
-}
-
-size_t dqrm_mlp_bwd_scratch_bytes(const dqrm_mlp* m, int64_t B) {
-    if (check_stack(m, "dqrm_mlp_bwd_scratch_bytes") || B < 0 || B > INT32_MAX) return 0;
-    return (size_t)2 * (size_t)B * (size_t)max_hidden(m) * sizeof(float);
-}
-
-int dqrm_mlp_bwd(const dqrm_mlp* m, const float* x, const float* const* y, const float* dy, int64_t B, float* dx,
-                 float* const* dw, float* const* db, void* scratch, size_t scratch_bytes, void* stream) {
-    const char* what = "dqrm_mlp_bwd";
-    int rc = check_stack(m, what);
-    if (rc) return rc;
-    if (B < 1 || B > INT32_MAX) return mlp_error(DQRM_E_INVALID, "%s: bad batch size", what);
-    if (!x || !dy) return mlp_error(DQRM_E_INVALID, "%s: null x / dy", what);
-    const int L = m->num_layers;
-    if ((rc = check_ptrs((const void* const*)y, L, "y", what))) return rc;
-    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
-    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
-    const size_t half = (size_t)B * (size_t)max_hidden(m) * sizeof(float);
-    if (half && (!scratch || scratch_bytes < 2 * half))
-        return mlp_error(DQRM_E_INVALID, "%s: scratch of %zu bytes, dqrm_mlp_bwd_scratch_bytes asks for %zu", what,
-                         scratch ? scratch_bytes : (size_t)0, 2 * half);
-    float* buf[2] = {(float*)scratch, (float*)((char*)scratch + half)};
-    for (int i = L - 1; i >= 0; --i) {
-        // layer i's dx is layer i-1's dy: buf[i & 1] is written while buf[(i + 1) & 1] is read
-        const float* dyi = i == L - 1 ? dy : buf[(i + 1) & 1];
-        float* dxi = i == 0 ? dx : buf[i & 1];
-        if ((rc = dqrm_linear_bwd_act(&m->layers[i], m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, y[i], dyi, B,
-                                      dxi, dw[i], db[i], stream)))
-            return rc;
-    }
-    return DQRM_OK;
-}
-
-size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* m) {
-    if (check_stack(m, "dqrm_mlp_sgd_workspace_bytes") || !has_tensor_layer(m)) return 0;
-    return (size_t)total_rows(m) * sizeof(float);
-}
-
-int dqrm_mlp_sgd(const dqrm_mlp* m, uint32_t flags, const float* const* dw, const float* const* db,
-                 const float* const* gscale, float lr, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* what = "dqrm_mlp_sgd";
-    int rc = check_stack(m, what);
-    if (rc) return rc;
-    if ((rc = check_flags(flags, DQRM_MLP_REQUANT, what))) return rc;
-    const int L = m->num_layers;
-    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
-    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
-    if (gscale && (rc = check_ptrs((const void* const*)gscale, L, "gscale", what))) return rc;
-    const int64_t rows = total_rows(m);
-    if (rows > INT32_MAX) return mlp_error(DQRM_E_CAPACITY, "%s: %lld weight rows exceed the grid's index range", what,
-                                           (long long)rows);
-    const bool requant = (flags & DQRM_MLP_REQUANT) != 0;
-    const bool two = requant && has_tensor_layer(m);
-    if (two && (!workspace || workspace_bytes < (size_t)rows * sizeof(float)))
-        return mlp_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, dqrm_mlp_sgd_workspace_bytes asks for %zu", what,
-                         workspace ? workspace_bytes : (size_t)0, (size_t)rows * sizeof(float));
-    SgdArgs a{};
-    for (int i = 0, row0 = 0; i < L; row0 += m->layers[i].out_features, ++i)
-        fill_layer(a.layer[i], &m->layers[i], requant && m->quantized[i], dw[i], db[i], gscale ? gscale[i] : nullptr,
-                   row0);
-    a.num_layers = L;
-    a.total_rows = (int)rows;
-    a.nlr = -lr;
-    a.rowmax = two ? (float*)workspace : nullptr;
-    return launch_sgd(a, two, (hipStream_t)stream);
-}
-
-size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num_stacks) {
-    const char* what = "dqrm_mlp_sgd_multi_workspace_bytes";
+// dqrm_mlp_sgd_workspace_bytes (one stack) and dqrm_mlp_sgd_multi_workspace_bytes
+size_t sgd_workspace_bytes(const dqrm_mlp* const* stacks, int num_stacks, const char* what) {
     if (check_stacks(stacks, num_stacks, what)) return 0;
     int64_t rows = 0;
     bool tensor = false;
@@ -390,10 +271,10 @@ size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num
     return tensor ? (size_t)rows * sizeof(float) : 0;
 }
 
-int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
-                       const float* const* db, const float* const* gscale, float lr, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    const char* what = "dqrm_mlp_sgd_multi";
+// dqrm_mlp_sgd (one stack) and dqrm_mlp_sgd_multi; ws_query: the export's workspace query, for the text
+int sgd_stacks(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
+               const float* const* db, const float* const* gscale, float lr, void* workspace, size_t workspace_bytes,
+               void* stream, const char* what, const char* ws_query) {
     int rc = check_stacks(stacks, num_stacks, what);
     if (rc) return rc;
     if ((rc = check_flags(flags, DQRM_MLP_REQUANT, what))) return rc;
@@ -408,13 +289,13 @@ int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t f
     if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
     if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
     if (gscale && (rc = check_ptrs((const void* const*)gscale, L, "gscale", what))) return rc;
-    if (rows > INT32_MAX) return mlp_error(DQRM_E_CAPACITY, "%s: %lld weight rows exceed the grid's index range", what,
+    if (rows > INT32_MAX) return set_error(DQRM_E_CAPACITY, "%s: %lld weight rows exceed the grid's index range", what,
                                            (long long)rows);
     const bool requant = (flags & DQRM_MLP_REQUANT) != 0;
     const bool two = requant && tensor;
     if (two && (!workspace || workspace_bytes < (size_t)rows * sizeof(float)))
-        return mlp_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, dqrm_mlp_sgd_multi_workspace_bytes asks for %zu",
-                         what, workspace ? workspace_bytes : (size_t)0, (size_t)rows * sizeof(float));
+        return set_error(DQRM_E_INVALID, "%s: workspace of %zu bytes, %s asks for %zu", what,
+                         workspace ? workspace_bytes : (size_t)0, ws_query, (size_t)rows * sizeof(float));
     // the stacks' layers back to back: one descriptor list, one grid over all their rows
     SgdArgs a{};
     int k = 0, row0 = 0;
@@ -431,9 +312,80 @@ int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t f
     return launch_sgd(a, two, (hipStream_t)stream);
 }
 
-// dqrm_model.hip validates its stacks before its first launch
-__attribute__((visibility("hidden"))) int dqrm_internal_check_mlp(const dqrm_mlp* m, const char* what) {
-    return check_stack(m, what);
+}  // namespace
+
+extern "C" {
+
+int dqrm_mlp_fwd(const dqrm_mlp* m, uint32_t flags, const float* x, int64_t B, float* const* y, void* stream) {
+    const char* what = "dqrm_mlp_fwd";
+    int rc = check_mlp(m, what);
+    if (rc) return rc;
+    if ((rc = check_flags(flags, DQRM_MLP_FRESH, what))) return rc;
+    if (B < 0 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!y) return set_error(DQRM_E_INVALID, "%s: null y array", what);
+    if (B == 0) return DQRM_OK;
+    if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);
+    if ((rc = check_ptrs((const void* const*)y, m->num_layers, "y", what))) return rc;
+    for (int i = 0; i < m->num_layers; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        if (m->quantized[i] && !(flags & DQRM_MLP_FRESH) && (rc = dqrm_linear_wquant(l, stream))) return rc;
+        if ((rc = dqrm_linear_fwd_act(l, m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, B, y[i], stream)))
+            return rc;
+    }
+    return DQRM_OK;
+}
+
+size_t dqrm_mlp_bwd_scratch_bytes(const dqrm_mlp* m, int64_t B) {
+    if (check_mlp(m, "dqrm_mlp_bwd_scratch_bytes") || B < 0 || B > INT32_MAX) return 0;
+    return (size_t)2 * (size_t)B * (size_t)max_hidden(m) * sizeof(float);
+}
+
+int dqrm_mlp_bwd(const dqrm_mlp* m, const float* x, const float* const* y, const float* dy, int64_t B, float* dx,
+                 float* const* dw, float* const* db, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* what = "dqrm_mlp_bwd";
+    int rc = check_mlp(m, what);
+    if (rc) return rc;
+    if (B < 1 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!x || !dy) return set_error(DQRM_E_INVALID, "%s: null x / dy", what);
+    const int L = m->num_layers;
+    if ((rc = check_ptrs((const void* const*)y, L, "y", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
+    const size_t half = (size_t)B * (size_t)max_hidden(m) * sizeof(float);
+    if (half && (!scratch || scratch_bytes < 2 * half))
+        return set_error(DQRM_E_INVALID, "%s: scratch of %zu bytes, dqrm_mlp_bwd_scratch_bytes asks for %zu", what,
+                         scratch ? scratch_bytes : (size_t)0, 2 * half);
+    float* buf[2] = {(float*)scratch, (float*)((char*)scratch + half)};
+    for (int i = L - 1; i >= 0; --i) {
+        // layer i's dx is layer i-1's dy: buf[i & 1] is written while buf[(i + 1) & 1] is read
+        const float* dyi = i == L - 1 ? dy : buf[(i + 1) & 1];
+        float* dxi = i == 0 ? dx : buf[i & 1];
+        if ((rc = dqrm_linear_bwd_act(&m->layers[i], m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, y[i], dyi, B,
+                                      dxi, dw[i], db[i], stream)))
+            return rc;
+    }
+    return DQRM_OK;
+}
+
+size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* m) {
+    return sgd_workspace_bytes(&m, 1, "dqrm_mlp_sgd_workspace_bytes");
+}
+
+int dqrm_mlp_sgd(const dqrm_mlp* m, uint32_t flags, const float* const* dw, const float* const* db,
+                 const float* const* gscale, float lr, void* workspace, size_t workspace_bytes, void* stream) {
+    return sgd_stacks(&m, 1, flags, dw, db, gscale, lr, workspace, workspace_bytes, stream, "dqrm_mlp_sgd",
+                      "dqrm_mlp_sgd_workspace_bytes");
+}
+
+size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num_stacks) {
+    return sgd_workspace_bytes(stacks, num_stacks, "dqrm_mlp_sgd_multi_workspace_bytes");
+}
+
+int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
+                       const float* const* db, const float* const* gscale, float lr, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return sgd_stacks(stacks, num_stacks, flags, dw, db, gscale, lr, workspace, workspace_bytes, stream,
+                      "dqrm_mlp_sgd_multi", "dqrm_mlp_sgd_multi_workspace_bytes");
 }
 
 }  // extern "C"

@@ -15,78 +15,62 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);            // dqrm_kernels.hip (hidden)
-extern "C" int dqrm_internal_check_mlp(const dqrm_mlp* m, const char* what);  // dqrm_mlp.hip (hidden)
-extern "C" int dqrm_internal_emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
-                                       int bits, uint32_t fwd_flags, int repack_bits, int training,
-                                       const char* who);                      // dqrm_kernels.hip (hidden)
-extern "C" int dqrm_internal_emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch,
-                                                  const dqrm_batch* next, uint32_t fwd_flags);
+#include "dqrm_internal.h"
 
 namespace {
+
+using namespace dqrm_internal;  // set_error and the stages' checks
 
 constexpr int64_t kMaxB = (int64_t)1 << 20;  // dqrm_loss_fwd's one workgroup
 constexpr uint32_t kStepFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_REQUANT | DQRM_MODEL_NO_UPDATE | DQRM_MODEL_EMB_READY;
 constexpr uint32_t kFwdFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_EMB_READY;
 
-int model_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dqrm_internal_set_error(code, buf);
-}
-
 // the struct alone: members, every stage's own rules, and the widths between the stages
 int check_model(const dqrm_model* m, const char* what) {
-    if (!m) return model_error(DQRM_E_INVALID, "%s: null model", what);
+    if (!m) return set_error(DQRM_E_INVALID, "%s: null model", what);
     if (!m->tables || !m->bottom || !m->top || !m->loss)
-        return model_error(DQRM_E_INVALID, "%s: null tables / bottom / top / loss", what);
-    int rc = dqrm_internal_emb_check(m->tables, nullptr, nullptr, m->embedding_bit, m->emb_fwd_flags, m->repack_bits, 0,
-                                     what);
+        return set_error(DQRM_E_INVALID, "%s: null tables / bottom / top / loss", what);
+    int rc = emb_check(m->tables, nullptr, nullptr, m->embedding_bit, m->emb_fwd_flags, m->repack_bits, 0,
+                       what);
     if (rc) return rc;
-    if ((rc = dqrm_internal_check_mlp(m->bottom, what))) return rc;
-    if ((rc = dqrm_internal_check_mlp(m->top, what))) return rc;
+    if ((rc = check_mlp(m->bottom, what))) return rc;
+    if ((rc = check_mlp(m->top, what))) return rc;
     const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
     if (Lb + Lt > DQRM_MLP_MAX_LAYERS)
-        return model_error(DQRM_E_INVALID, "%s: bottom and top have %d layers in all, at most %d fit the update's launch",
-                           what, Lb + Lt, DQRM_MLP_MAX_LAYERS);
+        return set_error(DQRM_E_INVALID, "%s: bottom and top have %d layers in all, at most %d fit the update's launch",
+                         what, Lb + Lt, DQRM_MLP_MAX_LAYERS);
     const int T = m->tables->num_tables, D = m->tables->dim;
     const dqrm_interact* ic = &m->interact;
     if (ic->num_features != T + 1 || ic->dim != D)
-        return model_error(DQRM_E_INVALID, "%s: interact needs num_features = tables + 1 = %d and dim = %d (got %d / %d)",
-                           what, T + 1, D, ic->num_features, ic->dim);
+        return set_error(DQRM_E_INVALID, "%s: interact needs num_features = tables + 1 = %d and dim = %d (got %d / %d)",
+                         what, T + 1, D, ic->num_features, ic->dim);
     if (ic->quant_bits != 0 && (ic->quant_bits < 2 || ic->quant_bits > 16))
-        return model_error(DQRM_E_INVALID, "%s: interact.quant_bits must be 0 or 2..16 (got %d)", what, ic->quant_bits);
+        return set_error(DQRM_E_INVALID, "%s: interact.quant_bits must be 0 or 2..16 (got %d)", what, ic->quant_bits);
     const int64_t R = dqrm_interact_out_features(T + 1, D, ic->self_interaction);  // F <= 64, D % 4
     if (R < 0) return (int)R;
     const dqrm_loss* lc = m->loss;
     if (lc->kind != DQRM_LOSS_BCE && lc->kind != DQRM_LOSS_MSE && lc->kind != DQRM_LOSS_WBCE)
-        return model_error(DQRM_E_INVALID, "%s: unknown loss kind %d (DQRM_LOSS_BCE / _MSE / _WBCE)", what, lc->kind);
+        return set_error(DQRM_E_INVALID, "%s: unknown loss kind %d (DQRM_LOSS_BCE / _MSE / _WBCE)", what, lc->kind);
     if (lc->kind == DQRM_LOSS_WBCE && (!lc->weights || lc->num_weights < 1))
-        return model_error(DQRM_E_INVALID, "%s: DQRM_LOSS_WBCE needs weights (num_weights >= 1, got %d)", what,
-                           lc->num_weights);
+        return set_error(DQRM_E_INVALID, "%s: DQRM_LOSS_WBCE needs weights (num_weights >= 1, got %d)", what,
+                         lc->num_weights);
     if (m->bottom->layers[Lb - 1].out_features != D)
-        return model_error(DQRM_E_INVALID, "%s: the bottom stack returns %d features, the tables' dim is %d", what,
-                           m->bottom->layers[Lb - 1].out_features, D);
+        return set_error(DQRM_E_INVALID, "%s: the bottom stack returns %d features, the tables' dim is %d", what,
+                         m->bottom->layers[Lb - 1].out_features, D);
     if (m->top->layers[0].in_features != R)
-        return model_error(DQRM_E_INVALID, "%s: the top stack takes %d features, the interaction returns %lld", what,
-                           m->top->layers[0].in_features, (long long)R);
+        return set_error(DQRM_E_INVALID, "%s: the top stack takes %d features, the interaction returns %lld", what,
+                         m->top->layers[0].in_features, (long long)R);
     if (m->top->layers[Lt - 1].out_features != 1)
-        return model_error(DQRM_E_INVALID, "%s: the top stack must return 1 feature (got %d)", what,
-                           m->top->layers[Lt - 1].out_features);
+        return set_error(DQRM_E_INVALID, "%s: the top stack must return 1 feature (got %d)", what,
+                         m->top->layers[Lt - 1].out_features);
     return DQRM_OK;
 }
 
 int check_B(int64_t B, const char* what) {
     if (B < 1 || B > kMaxB)
-        return model_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
+        return set_error(DQRM_E_INVALID, "%s: B must be 1..%lld (got %lld)", what, (long long)kMaxB, (long long)B);
     return DQRM_OK;
 }
 
@@ -128,8 +112,8 @@ void cut_workspace(const dqrm_model* m, int64_t B, int64_t max_lookups, Cut* c) 
 
 int check_workspace(const Cut& c, const void* ws, size_t bytes, const char* what) {
     if (!ws || ((uintptr_t)ws & 15) || bytes < c.total)
-        return model_error(DQRM_E_WORKSPACE, "%s: workspace needs %zu bytes, 16-B aligned (got %zu)", what, c.total,
-                           ws ? bytes : (size_t)0);
+        return set_error(DQRM_E_WORKSPACE, "%s: workspace needs %zu bytes, 16-B aligned (got %zu)", what, c.total,
+                         ws ? bytes : (size_t)0);
     return DQRM_OK;
 }
 
@@ -138,23 +122,23 @@ int check_call(const dqrm_model* m, const dqrm_batch* batch, const dqrm_batch* n
                int training, const char* what) {
     int rc = check_model(m, what);
     if (rc) return rc;
-    if (flags & ~known) return model_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
-    if (!batch) return model_error(DQRM_E_INVALID, "%s: null batch", what);
-    if ((rc = dqrm_internal_emb_check(m->tables, batch, next, m->embedding_bit, m->emb_fwd_flags, m->repack_bits,
-                                      training, what)))
+    if (flags & ~known) return set_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    if (!batch) return set_error(DQRM_E_INVALID, "%s: null batch", what);
+    if ((rc = emb_check(m->tables, batch, next, m->embedding_bit, m->emb_fwd_flags, m->repack_bits,
+                        training, what)))
         return rc;
     if ((rc = check_B(batch->num_bags, what))) return rc;
-    if (batch->max_lookups < 0) return model_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
+    if (batch->max_lookups < 0) return set_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
     // the interaction's piece index (dqrm_interact.hip's check_batch)
     if (batch->num_bags > (int64_t)INT32_MAX / ((int64_t)m->interact.num_features * (m->interact.dim / 4)))
-        return model_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
-                           (long long)batch->num_bags);
+        return set_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
+                         (long long)batch->num_bags);
     if (next) {
         if (flags & DQRM_MODEL_NO_UPDATE)
-            return model_error(DQRM_E_INVALID, "%s: a next batch needs the update (DQRM_MODEL_NO_UPDATE is set)", what);
+            return set_error(DQRM_E_INVALID, "%s: a next batch needs the update (DQRM_MODEL_NO_UPDATE is set)", what);
         if (next->num_bags != batch->num_bags)
-            return model_error(DQRM_E_INVALID, "%s: next has %lld bags, the slab holds %lld", what,
-                               (long long)next->num_bags, (long long)batch->num_bags);
+            return set_error(DQRM_E_INVALID, "%s: next has %lld bags, the slab holds %lld", what,
+                             (long long)next->num_bags, (long long)batch->num_bags);
     }
     return DQRM_OK;
 }
@@ -164,12 +148,6 @@ int wquant_launches(const dqrm_mlp* s) {
     for (int i = 0; i < s->num_layers; ++i)
         if (s->quantized[i]) n += s->layers[i].per_channel ? 1 : 2;
     return n;
-}
-
-bool has_tensor_layer(const dqrm_mlp* s) {
-    for (int i = 0; i < s->num_layers; ++i)
-        if (s->quantized[i] && !s->layers[i].per_channel) return true;
-    return false;
 }
 
 // the forward both calls share; g == NULL and labels == NULL as dqrm_model_fwd passes them
@@ -215,8 +193,8 @@ int dqrm_model_workspace_layout(const dqrm_model* m, int64_t B, int64_t max_look
     int rc = check_model(m, what);
     if (rc) return rc;
     if ((rc = check_B(B, what))) return rc;
-    if (max_lookups < 0) return model_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
-    if (!out) return model_error(DQRM_E_INVALID, "%s: null out", what);
+    if (max_lookups < 0) return set_error(DQRM_E_INVALID, "%s: negative max_lookups", what);
+    if (!out) return set_error(DQRM_E_INVALID, "%s: null out", what);
     Cut c;
     cut_workspace(m, B, max_lookups, &c);
     out->slab = c.slab;
@@ -239,8 +217,8 @@ int dqrm_model_fwd(const dqrm_model* m, const dqrm_batch* batch, uint32_t flags,
     const char* what = "dqrm_model_fwd";
     int rc = check_call(m, batch, nullptr, flags, kFwdFlags, 0, what);
     if (rc) return rc;
-    if (!x) return model_error(DQRM_E_INVALID, "%s: null x", what);
-    if (labels && !loss) return model_error(DQRM_E_INVALID, "%s: labels need a loss to write (null loss)", what);
+    if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);
+    if (labels && !loss) return set_error(DQRM_E_INVALID, "%s: labels need a loss to write (null loss)", what);
     Cut c;
     cut_workspace(m, batch->num_bags, batch->max_lookups, &c);
     if ((rc = check_workspace(c, workspace, workspace_bytes, what))) return rc;
@@ -257,11 +235,11 @@ int dqrm_model_step(const dqrm_model* m, const dqrm_batch* batch, const dqrm_bat
     const char* what = "dqrm_model_step";
     int rc = check_call(m, batch, next, flags, kStepFlags, 1, what);
     if (rc) return rc;
-    if (!x || !labels || !loss || !g) return model_error(DQRM_E_INVALID, "%s: null x / labels / loss / g", what);
+    if (!x || !labels || !loss || !g) return set_error(DQRM_E_INVALID, "%s: null x / labels / loss / g", what);
     const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
-    if (!dw || !db) return model_error(DQRM_E_INVALID, "%s: null dw / db array", what);
+    if (!dw || !db) return set_error(DQRM_E_INVALID, "%s: null dw / db array", what);
     for (int i = 0; i < Lb + Lt; ++i)
-        if (!dw[i] || !db[i]) return model_error(DQRM_E_INVALID, "%s: null dw[%d] / db[%d]", what, i, i);
+        if (!dw[i] || !db[i]) return set_error(DQRM_E_INVALID, "%s: null dw[%d] / db[%d]", what, i, i);
     Cut c;
     cut_workspace(m, batch->num_bags, batch->max_lookups, &c);
     if ((rc = check_workspace(c, workspace, workspace_bytes, what))) return rc;
@@ -309,7 +287,7 @@ int dqrm_model_step_launches(const dqrm_model* m, const dqrm_batch* batch, const
     n += 1;                                                             // dqrm_loss_fwd
     n += 2 * Lt + 1 + (2 * Lb - 1);                                     // top bwd, interact bwd, bottom bwd
     if (flags & DQRM_MODEL_NO_UPDATE) return n;
-    n += dqrm_internal_emb_bwd_sgd_launches(m->tables, batch, next, m->emb_fwd_flags);
+    n += emb_bwd_sgd_launches(m->tables, batch, next, m->emb_fwd_flags);
     n += 1 + ((flags & DQRM_MODEL_REQUANT) && (has_tensor_layer(m->bottom) || has_tensor_layer(m->top)) ? 1 : 0);
     return n;
 }

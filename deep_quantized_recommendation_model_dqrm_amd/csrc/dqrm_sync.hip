@@ -19,10 +19,11 @@
 #include <stdint.h>
 
 #include "../../include/dqrm.h"
-
-extern "C" int dqrm_internal_set_error(int code, const char* msg);
+#include "dqrm_internal.h"
 
 namespace {
+
+using dqrm_internal::set_error;
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
     x += 0x9E3779B97F4A7C15ull;
@@ -84,21 +85,21 @@ extern "C" {
 
 int dqrm_checksum64(const void* data, int64_t num_words, uint64_t* out, void* stream) {
     if (!out || num_words < 0 || (num_words > 0 && !data) || (((uintptr_t)data) & 15))
-        return dqrm_internal_set_error(DQRM_E_INVALID, "dqrm_checksum64: bad arguments (data 16-B aligned)");
+        return set_error(DQRM_E_INVALID, "dqrm_checksum64: bad arguments (data 16-B aligned)");
     if (num_words == 0) return DQRM_OK;
     hipLaunchKernelGGL(k_checksum64, dim3(grid_of(num_words / 4 + 1)), dim3(256), 0, (hipStream_t)stream,
                        (const uint32_t*)data, num_words, (unsigned long long*)out);
-    if (hipGetLastError() != hipSuccess) return dqrm_internal_set_error(DQRM_E_HIP, "dqrm_checksum64: launch failed");
+    if (hipGetLastError() != hipSuccess) return set_error(DQRM_E_HIP, "dqrm_checksum64: launch failed");
     return DQRM_OK;
 }
 
 int dqrm_replica_mean(float* data, int64_t n, int num_replicas, float inv_n, void* stream) {
     if (num_replicas < 1 || n < 0 || (n > 0 && !data) || (((uintptr_t)data) & 15))
-        return dqrm_internal_set_error(DQRM_E_INVALID, "dqrm_replica_mean: bad arguments (data 16-B aligned)");
+        return set_error(DQRM_E_INVALID, "dqrm_replica_mean: bad arguments (data 16-B aligned)");
     if (n == 0) return DQRM_OK;
     hipLaunchKernelGGL(k_replica_mean, dim3(grid_of(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, data, n,
                        num_replicas, inv_n);
-    if (hipGetLastError() != hipSuccess) return dqrm_internal_set_error(DQRM_E_HIP, "dqrm_replica_mean: launch failed");
+    if (hipGetLastError() != hipSuccess) return set_error(DQRM_E_HIP, "dqrm_replica_mean: launch failed");
     return DQRM_OK;
 }
 

@@ -132,6 +132,14 @@ def apply_mlp(x, layers, prev_act_scaling_factor=None):
 
 
 # ------------------------------------------------------------------ the stack as one host call
+def _on_device(dev, fn, *args):
+    """fn(*args) with dev as torch's current device."""
+    if dev.index != torch.cuda.current_device():
+        with torch.cuda.device(dev):
+            return fn(*args)
+    return fn(*args)
+
+
 class _StackFn(torch.autograd.Function):
     """One autograd node for a whole stack, over (x, *weights, *biases): one dqrm_mlp_fwd and one
     dqrm_mlp_bwd. Every layer's output is a torch tensor saved for the backward (an activation's
@@ -300,25 +308,20 @@ class MLPStack:
                 l._scale_buffer()
         return dev
 
-    def _on(self, dev, fn, *args):
-        if dev.index != torch.cuda.current_device():
-            with torch.cuda.device(dev):
-                return fn(*args)
-        return fn(*args)
-
     # ------------------------------------------------------------ forward
-    def is_fresh(self) -> bool:
-        """Whether the next forward will skip the weight quantization."""
-        return self._fresh is not None and self._fresh == self._state()
+    def is_fresh(self, key=None) -> bool:
+        """Whether the next forward will skip the weight quantization (key: ``_key()``, from a
+        caller that has just computed it)."""
+        return self._fresh is not None and self._fresh == self._state(key)
 
     def __call__(self, x):
         self._prepare(x)
-        return self._on(x.device, self._run, x)
+        return _on_device(x.device, self._run, x)
 
     def _run(self, x):
         key = self._key()
         c = self._c_struct(key)  # raises on an unsupported layer before autograd is involved
-        fresh = self._fresh is not None and self._fresh == self._state(key)
+        fresh = self.is_fresh(key)
         if not fresh:
             self._fresh = None
         ws = [l.weight for l in self.layers]
@@ -354,7 +357,7 @@ class MLPStack:
                     raise ValueError(f"grad_scales[{i}] must be a contiguous float32 tensor of "
                                      f"{l.out_features + 1} elements on {l.weight.device}")
             gs = self._PtrArray(*[s.data_ptr() for s in grad_scales])
-        self._on(dev, self._sgd, float(lr), bool(requantize), gs)
+        _on_device(dev, self._sgd, float(lr), bool(requantize), gs)
 
     def _sgd(self, lr, requantize, gs):
         key = self._key()
@@ -380,7 +383,7 @@ class MLPStack:
         """Run every quantized layer's dqrm_linear_wquant now and mark the stack fresh: an
         inference loop's forwards then launch no quantization at all."""
         dev = self._prepare()
-        self._on(dev, self._requantize)
+        _on_device(dev, self._requantize)
 
     def _requantize(self):
         self._c_struct()

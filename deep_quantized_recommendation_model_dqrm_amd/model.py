@@ -30,7 +30,7 @@ from torch import nn
 from . import _lib as L
 from .interaction import DotInteraction, out_features
 from .loss import DLRMLoss
-from .mlp import MLPStack, create_mlp
+from .mlp import MLPStack, _on_device, create_mlp
 from .quant_modules_not_quantize_grad import error_check_due, poll_device_errors
 from .tables import EmbeddingTableSet, LookupBatch, _stream_handle
 
@@ -307,23 +307,16 @@ class DQRMNet(nn.Module):
         return self.top_stack(self.interact(x, slab))
 
     # ------------------------------------------------------------ one host call
-    def _on(self, dev, fn, *args):
-        if dev.index != torch.cuda.current_device():
-            with torch.cuda.device(dev):
-                return fn(*args)
-        return fn(*args)
-
     def predict(self, dense_x, batch, labels=None):
         """The forward as ONE host call (dqrm_model_fwd): p ``[B, 1]`` without labels, ``(E, Z)``
         with them: the 0-dim loss and the clamped prediction. Quantizes the MLP weights only when
         the stacks are not fresh (``requantize()`` makes them so)."""
         dev, B = self._check_inputs(dense_x, batch, labels, "predict")
-        return self._on(dev, self._predict, dense_x, batch, labels, dev, B)
+        return _on_device(dev, self._predict, dense_x, batch, labels, dev, B)
 
     def _predict(self, dense_x, batch, labels, dev, B):
         kb, kt, m = self._prepare("predict")
-        fresh = self.bot_stack._fresh is not None and self.top_stack._fresh is not None \
-            and self.bot_stack._fresh == self.bot_stack._state(kb) and self.top_stack._fresh == self.top_stack._state(kt)
+        fresh = self.bot_stack.is_fresh(kb) and self.top_stack.is_fresh(kt)
         ws = self._workspace(m, B, batch.max_lookups, dev)
         self.__dict__["_prefetched"] = None  # the slab is overwritten
         self._poll()
@@ -384,13 +377,12 @@ class DQRMNet(nn.Module):
             if next_batch.num_bags != B or next_batch.idx.device != dev:
                 raise ValueError(f"DQRMNet.train_step: next_batch has {next_batch.num_bags} bags, batch {B} "
                                  "(the prefetched forward shares the slab)")
-        return self._on(dev, self._train_step, dense_x, batch, labels, float(lr), next_batch, bool(update), dev, B)
+        return _on_device(dev, self._train_step, dense_x, batch, labels, float(lr), next_batch, bool(update), dev, B)
 
     def _train_step(self, dense_x, batch, labels, lr, next_batch, update, dev, B):
         bot, top, tables = self.bot_stack, self.top_stack, self.tables
         kb, kt, m = self._prepare("train_step")
-        fresh = bot._fresh is not None and top._fresh is not None and bot._fresh == bot._state(kb) \
-            and top._fresh == top._state(kt)
+        fresh = bot.is_fresh(kb) and top.is_fresh(kt)
         pf = self.__dict__["_prefetched"]
         ready = pf is not None and pf[0] is batch and pf[1] == tables.write_epoch and pf[2] == B
         # sized for the next batch too, so that its step finds its slab where this one leaves it

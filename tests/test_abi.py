@@ -35,6 +35,16 @@ def test_library_exports_every_header_symbol(lib):
     assert lib.dqrm_abi_version() == L.DQRM_ABI_VERSION
 
 
+def test_library_exports_nothing_internal(lib):
+    """What csrc/dqrm_internal.h declares stays inside the library: the C ABI has no symbol that
+    begins with dqrm_internal."""
+    src = open(os.path.join(ROOT, "deep_quantized_recommendation_model_dqrm_amd", "csrc", "dqrm_internal.h")).read()
+    names = set(re.findall(r"\b([a-z][a-z0-9_]*)\(", re.sub(r"//[^\n]*", "", src)))
+    assert {"set_error", "check_linear", "check_act", "check_mlp", "emb_check", "launch_quant_pack"} <= names, names
+    for name in sorted(names):
+        assert not hasattr(lib, "dqrm_internal_" + name), name
+
+
 def test_payload_bytes_agree(lib):
     for T, cap, D, bits in [(26, 3328, 16, 8), (26, 53248, 64, 8), (4, 7, 4, 16), (3, 0, 32, 32), (1, 1, 256, 2)]:
         assert lib.dqrm_payload_bytes(T, cap, D, bits) == payload_bytes(T, cap, D, bits)
