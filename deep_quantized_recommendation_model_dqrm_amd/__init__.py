@@ -14,6 +14,9 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
                                                                 bits depend on the batch size alone)
   * ``DLRM_Net`` itself and one iteration of its training loop  (``DQRMNet``: the stages above as one
                                                                 model, ``train_step`` one host call)
+  * ``inference()``'s accuracy count and ``roc_auc_score``     (``DLRMMetrics`` / ``DQRMNet.evaluate``: the
+                                                                test loop's two numbers from integers kept
+                                                                on the device, the AUC exact)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
@@ -33,6 +36,7 @@ from .mlp import FusedActivation, MLPStack, apply_mlp, create_mlp, fuse_activati
 from .interaction import DotInteraction, interact_features
 from .loss import DLRMLoss, loss_fn_wrap
 from .model import DQRMNet
+from .metrics import DLRMMetrics
 from . import quantized_ops
 
 __all__ = [
@@ -64,6 +68,7 @@ __all__ = [
     "DLRMLoss",
     "loss_fn_wrap",
     "DQRMNet",
+    "DLRMMetrics",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

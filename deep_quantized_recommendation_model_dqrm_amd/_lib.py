@@ -74,6 +74,12 @@ DQRM_LOSS_MSE = 1
 DQRM_LOSS_WBCE = 2
 DQRM_LOSS_MAX_BATCH = 1 << 20  # dqrm_loss_fwd's one workgroup
 
+DQRM_METRICS_MAX_SAMPLES = 1 << 30
+DQRM_METRICS_SORT_TILE = 4096
+DQRM_METRICS_F_LABEL = 1
+DQRM_METRICS_F_NONFINITE = 2
+DQRM_METRICS_F_COUNT = 4
+
 DQRM_ABI_VERSION = 12  # include/dqrm.h
 DQRM_PRESUM_MAX_LOOKUPS = 2048
 
@@ -133,6 +139,11 @@ EXPORTED_SYMBOLS = (
     "dqrm_model_fwd",
     "dqrm_model_step",
     "dqrm_model_step_launches",
+    "dqrm_metrics_reset",
+    "dqrm_metrics_update",
+    "dqrm_metrics_workspace_bytes",
+    "dqrm_metrics_finish",
+    "dqrm_metrics_finish_launches",
     "dqrm_act_quant_workspace_bytes",
     "dqrm_act_quant_fwd",
     "dqrm_act_quant_bwd",
@@ -319,6 +330,22 @@ class ModelLayout(C.Structure):
     _fields_ = [(name, C.c_size_t) for name in ("slab", "r", "p", "dr", "dx", "demb", "total")]
 
 
+class Metrics(C.Structure):
+    """Mirror of ``dqrm_metrics`` (include/dqrm.h)."""
+
+    _fields_ = [
+        ("capacity", C.c_int64),
+        ("keys", C.c_void_p),
+        ("counters", C.c_void_p),
+    ]
+
+
+class MetricsResult(C.Structure):
+    """Mirror of ``dqrm_metrics_result`` (include/dqrm.h): what dqrm_metrics_finish writes."""
+
+    _fields_ = [(name, C.c_uint64) for name in ("n_pos", "n_neg", "n_correct", "twice_u", "flags")]
+
+
 class Exchange(C.Structure):
     """Mirror of ``dqrm_exchange`` (include/dqrm.h): one rank's exchange buffers."""
 
@@ -481,6 +508,11 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_model_fwd": (C.c_int, [MO, BA, C.c_uint32, P, P, P, P, P, C.c_size_t, P]),
         "dqrm_model_step": (C.c_int, [MO, BA, BA, C.c_uint32, P, P, C.c_float, P, P, P, PP, PP, P, C.c_size_t, P]),
         "dqrm_model_step_launches": (C.c_int, [MO, BA, BA, C.c_uint32]),
+        "dqrm_metrics_reset": (C.c_int, [C.POINTER(Metrics), P]),
+        "dqrm_metrics_update": (C.c_int, [C.POINTER(Metrics), P, P, C.c_int64, C.c_int64, P]),
+        "dqrm_metrics_workspace_bytes": (C.c_size_t, [C.c_int64]),
+        "dqrm_metrics_finish": (C.c_int, [C.POINTER(Metrics), C.c_int64, P, P, C.c_size_t, P]),
+        "dqrm_metrics_finish_launches": (C.c_int, [C.c_int64]),
         "dqrm_act_quant_workspace_bytes": (C.c_int64, [C.c_int64]),
         "dqrm_act_quant_fwd": (C.c_int, [AQ, P, C.c_int64, P, P, P]),
         "dqrm_act_quant_bwd": (C.c_int, [P, P, C.c_int64, P, P]),

@@ -332,6 +332,57 @@ class DQRMNet(nn.Module):
             return loss, z
         return self._view(ws, m, B, batch.max_lookups, "p").clone()
 
+    def evaluate(self, batches, metrics=None, max_batches=-1):
+        """The reference's test loop (``inference()``, :1304-1404) with every score left on the
+        device: per batch dqrm_model_fwd with the labels, whose clamped prediction Z goes straight
+        into ``DLRMMetrics.update`` (no clone, no sync), then ``compute()``'s dict: ``n``, ``n_pos``,
+        ``n_correct``, ``test_acc`` and the exact ``roc_auc``.
+
+        batches: an iterable of ``(dense_x, LookupBatch, labels)``; max_batches > 0 stops after that
+        many (the reference's ``nbatches``, :1327). metrics: a ``DLRMMetrics`` to use (it is reset), or
+        None: one is made for ``len(batches)`` times the first batch's size, so ``batches`` must then
+        have a ``len`` and no later batch may be larger. Both stacks are requantized once
+        beforehand if they are not fresh, which changes no bits and saves the per-batch weight
+        quantization. A prefetched embedding forward is discarded, as by ``predict``. Every rank of a
+        larger world evaluates what it is given."""
+        from .metrics import DLRMMetrics
+
+        if metrics is not None and not isinstance(metrics, DLRMMetrics):
+            raise TypeError("DQRMNet.evaluate: metrics must be a DLRMMetrics (or None)")
+        max_batches = int(max_batches)
+        if metrics is None:
+            try:
+                nb = len(batches)
+            except TypeError:
+                raise ValueError("DQRMNet.evaluate: batches has no len(), so the metrics cannot be sized: pass "
+                                 "metrics=DLRMMetrics(capacity)") from None
+            if max_batches > 0:
+                nb = min(nb, max_batches)
+        dev = self._device("evaluate")
+        if metrics is not None:
+            if metrics.device != dev:
+                raise ValueError(f"DQRMNet.evaluate: metrics on {metrics.device} but the model on {dev}")
+            metrics.reset()
+        kb, kt, _ = self._prepare("evaluate")
+        if not (self.bot_stack.is_fresh(kb) and self.top_stack.is_fresh(kt)):
+            self.requantize()
+        seen = 0
+        for k, item in enumerate(batches):
+            if 0 < max_batches <= k:
+                break
+            dense_x, batch, labels = item
+            if labels is None:
+                raise ValueError("DQRMNet.evaluate: every batch needs its labels")
+            dev, B = self._check_inputs(dense_x, batch, labels, "evaluate")
+            if metrics is None:
+                metrics = DLRMMetrics(max(nb, 1) * B, device=dev)
+            _, Z = _on_device(dev, self._predict, dense_x, batch, labels, dev, B)
+            metrics.update(Z, labels)
+            seen += 1
+        if seen == 0:
+            raise ValueError("DQRMNet.evaluate: no batch given")
+        return metrics.compute()
+
     def requantize(self):
         """Quantize both stacks' weights now and mark them fresh (``MLPStack.requantize``)."""
         self._device("requantize")

@@ -87,7 +87,11 @@ extern "C" {
                                   likewise within 12: the whole model per call, dqrm_model (DQRMNet):
                                   dqrm_mlp_sgd_multi_workspace_bytes, dqrm_mlp_sgd_multi,
                                   dqrm_model_workspace_bytes, dqrm_model_workspace_layout,
-                                  dqrm_model_fwd, dqrm_model_step, dqrm_model_step_launches */
+                                  dqrm_model_fwd, dqrm_model_step, dqrm_model_step_launches;
+                                  likewise within 12: the test loop's metrics, dqrm_metrics
+                                  (DLRMMetrics): dqrm_metrics_reset, dqrm_metrics_update,
+                                  dqrm_metrics_workspace_bytes, dqrm_metrics_finish,
+                                  dqrm_metrics_finish_launches */
 
 /* status codes */
 #define DQRM_OK            0
@@ -1025,6 +1029,93 @@ int dqrm_model_step(const dqrm_model* model, const dqrm_batch* batch, const dqrm
                     float* const* dw, float* const* db, void* workspace, size_t workspace_bytes, void* stream);
 int dqrm_model_step_launches(const dqrm_model* model, const dqrm_batch* batch, const dqrm_batch* next,
                              uint32_t flags);
+
+/* ---------------------------------------------------------------------------------
+ * DLRMMetrics: the two numbers of the reference's test loop, test accuracy and ROC AUC
+ * (inference(), dlrm_s_pytorch_tb_dp_one_parallel_comm.py:1304-1404), kept on the device,
+ * csrc/dqrm_metrics.hip. Per test batch the reference synchronises, copies scores and targets
+ * to the host (:1348-1355), counts np.round(S, 0) == T (:1358-1360) and at the end calls
+ * sklearn.metrics.roc_auc_score on the concatenated arrays (:1387). Here a batch is one launch
+ * that nothing waits for, and the end is a fixed number of launches plus one 40-byte result.
+ *
+ * The arithmetic, for a stream of (z, t) pairs, both f32:
+ *   n_correct  #{ rintf(z) == t }: np.round(S, 0) == T in f32, ties to even (0.5 -> 0, 1.5 -> 2)
+ *   key        s = z + 0.0f (-0 ties with +0, as in sklearn); b = bits(s);
+ *              key = b >> 31 ? ~b : b | 0x80000000: a uint32 whose unsigned order is the order of
+ *              the finite floats
+ *   class      t == 1.0f positive, t == 0.0f negative; any other t sets DQRM_METRICS_F_LABEL (the
+ *              sample enters neither class); a non-finite z sets DQRM_METRICS_F_NONFINITE. A
+ *              flagged sample still counts in the caller's n; a set flag makes the result invalid
+ *   twice_u    sum over positives i of 2 * #{negatives j: key_j < key_i} + #{negatives j: key_j ==
+ *              key_i}, a uint64: twice the Mann-Whitney U with ties counted one half
+ *   roc_auc    twice_u / (2 * n_pos * n_neg), ONE float64 division, done by the caller: the area
+ *              sklearn's trapezoid over roc_curve computes
+ * Nothing on the device is floating-point arithmetic except rintf, the compares and + 0.0f, and
+ * every sum is an integer sum. Where a key lands in `keys` depends on the order in which waves
+ * arrive; n_pos, n_neg, n_correct, twice_u and flags are functions of the MULTISET of samples
+ * alone: batch order, batch size, grid and arrival order do not enter their bits.
+ *
+ * State (the struct is HOST memory, its pointers device memory): keys[capacity], positives
+ * appended from the front, negatives from the back; counters[4] = n_pos, n_neg, n_correct, flags.
+ * dqrm_metrics_reset zeroes the counters (one 32-byte memset, no launch).
+ *
+ * dqrm_metrics_update (the loop body, :1348-1360): ONE launch for a batch of n samples, z[n] and
+ * t[n]. seen_before: the samples of the updates since the reset (the caller's sum of batch
+ * sizes). A wave reserves its range with a ballot count and one returning device-scope atomic add
+ * per class; n_correct and the flags take one integer atomic per workgroup.
+ *
+ * dqrm_metrics_finish (:1366, :1387): seen = the samples of all updates since the reset, known to
+ * the host, so every grid is sized from it and nothing is read back. The kernels read n_pos and
+ * n_neg from the counters, sort the SMALLER class (at most seen / 2 keys; n_pos == n_neg: the
+ * positives) in place by an LSD radix sort of four 8-bit passes that ping-pongs through the
+ * workspace (per pass: tile histograms of DQRM_METRICS_SORT_TILE keys, a scan, a stable scatter;
+ * bare keys without payload, so the sorted bytes are those of any correct sort), then every
+ * element of the other class does a lower-bound and an upper-bound search (lb, ub) in it: a
+ * positive adds lb + ub when the negatives are sorted, a negative adds 2 * n_pos - lb - ub when
+ * the positives are; both sums are twice_u. The last launch writes *out_dev. Surplus workgroups
+ * exit. The state stays valid (the order inside a class is not part of it): updates may follow
+ * and finish may be called again. Counters that contradict `seen` or `capacity` (a caller that
+ * passed wrong counts) set DQRM_METRICS_F_COUNT in the result; nothing is then sorted.
+ * dqrm_metrics_finish_launches: its kernel launches (a constant for every valid seen), <0 for
+ * seen < 1.
+ *
+ * workspace: 16-byte aligned, dqrm_metrics_workspace_bytes(seen) bytes (0 for seen outside
+ * 1..DQRM_METRICS_MAX_SAMPLES), contents irrelevant; the size grows with seen.
+ *
+ * Every argument is checked before any launch: a rejected call writes nothing. DQRM_E_INVALID: a
+ * null struct or member, capacity outside 1..DQRM_METRICS_MAX_SAMPLES, null z / t / out_dev,
+ * n < 1, seen_before < 0, seen_before + n > capacity, seen < 1 or > capacity. DQRM_E_WORKSPACE: a
+ * null, misaligned or short workspace. No call allocates, synchronises or reads back.
+ * ------------------------------------------------------------------------------ */
+#define DQRM_METRICS_MAX_SAMPLES (1ll << 30)
+#define DQRM_METRICS_SORT_TILE   4096   /* keys per workgroup of a sort pass */
+#define DQRM_METRICS_F_LABEL     1u     /* a target that is neither 0.0f nor 1.0f */
+#define DQRM_METRICS_F_NONFINITE 2u     /* a NaN or infinite score */
+#define DQRM_METRICS_F_COUNT     4u     /* the device counters contradict seen / capacity */
+
+typedef struct dqrm_metrics {
+    int64_t   capacity;    /* samples `keys` holds, 1..DQRM_METRICS_MAX_SAMPLES */
+    uint32_t* keys;        /* [capacity] */
+    uint64_t* counters;    /* [4] n_pos, n_neg, n_correct, flags */
+} dqrm_metrics;
+
+typedef struct dqrm_metrics_result {
+    uint64_t n_pos, n_neg, n_correct, twice_u, flags;
+} dqrm_metrics_result;
+
+/* test_accu = 0, scores = [], targets = [] (:1317-1321): a 32-byte memset, no launch. */
+int dqrm_metrics_reset(const dqrm_metrics* m, void* stream);
+/* The loop body after the forward (:1347-1361): no synchronize, no copy; one launch. */
+int dqrm_metrics_update(const dqrm_metrics* m, const float* z, const float* t, int64_t n, int64_t seen_before,
+                        void* stream);
+/* 0 for seen outside 1..DQRM_METRICS_MAX_SAMPLES (dqrm_last_error says why). */
+size_t dqrm_metrics_workspace_bytes(int64_t seen);
+/* acc_test's numerator (:1366) and np.concatenate + roc_auc_score (:1385-1387) as integers in
+ * *out_dev (device memory, 40 bytes); the two divisions are the caller's. */
+int dqrm_metrics_finish(const dqrm_metrics* m, int64_t seen, dqrm_metrics_result* out_dev, void* ws,
+                        size_t ws_bytes, void* stream);
+/* Kernel launches of dqrm_metrics_finish (memsets not counted), <0 for seen it rejects. */
+int dqrm_metrics_finish_launches(int64_t seen);
 
 /* ---------------------------------------------------------------------------------
  * Row-wise PTQ formats of the reference's inference path.
