@@ -86,6 +86,7 @@ DQRM_INLINE void merge_forward(const dqrm_internal::MergeApplyArgs& a, int t, in
     const int64_t* idx = a.fwd_idx + (int64_t)t * B;
     float* out = a.fwd_out + (int64_t)t * a.fwd_ost_t;
     const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    const bool wty = (a.wt & WT_Y) != 0;
     for (int64_t b0 = (int64_t)bx * (G * FWD_UNR); b0 < B; b0 += (int64_t)a.fwd_gx * (G * FWD_UNR)) {
         int64_t x[FWD_UNR];
 #pragma unroll
@@ -99,10 +100,7 @@ DQRM_INLINE void merge_forward(const dqrm_internal::MergeApplyArgs& a, int t, in
             const bool ok = x[k] >= 0 && x[k] < nrows;
             v[k] = nrows > 0 ? ld4_wt(a.W + (rb + (ok ? x[k] : 0)) * D + sub * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-#pragma unroll
-        for (int k = 0; k < FWD_UNR; ++k) {
-            const int64_t b = b0 + k * G + grp;
-            if (b >= B) continue;
+        auto row_out = [&](int k) -> float4 {
             const bool ok = x[k] >= 0 && x[k] < nrows;
             if (!ok && sub == 0) flag_error(a.err, DQRM_ERRF_INDEX);
             float4 y = ok ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -112,7 +110,24 @@ DQRM_INLINE void merge_forward(const dqrm_internal::MergeApplyArgs& a, int t, in
                 y.z = fake_quant(y.z, rr, qlo, qhi) * sv;
                 y.w = fake_quant(y.w, rr, qlo, qhi) * sv;
             }
-            reinterpret_cast<float4*>(out + b * a.fwd_ost_b)[sub] = y;
+            return y;
+        };
+        if (wty) {
+            // write-through: every row quantized before the first store (a wait for a row must not
+            // cover an asm store the compiler does not count: st4_wt)
+#pragma unroll
+            for (int k = 0; k < FWD_UNR; ++k)
+                if (b0 + k * G + grp < B) v[k] = row_out(k);
+#pragma unroll
+            for (int k = 0; k < FWD_UNR; ++k)
+                if (b0 + k * G + grp < B) st4_wt(reinterpret_cast<float4*>(out + (b0 + k * G + grp) * a.fwd_ost_b) + sub, v[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < FWD_UNR; ++k) {
+                const int64_t b = b0 + k * G + grp;
+                if (b >= B) continue;
+                reinterpret_cast<float4*>(out + b * a.fwd_ost_b)[sub] = row_out(k);
+            }
         }
     }
     // every forward workgroup of the table has passed the gate once the last one arrives here:
@@ -514,7 +529,9 @@ __global__ void __launch_bounds__(AP_TPB) k_apply_pos(dqrm_internal::MergeApplyA
 
 namespace dqrm_internal {
 
-hipError_t launch_apply_merge(const MergeApplyArgs& a, hipStream_t stream) {
+hipError_t launch_apply_merge(const MergeApplyArgs& a0, hipStream_t stream) {
+    MergeApplyArgs a = a0;
+    a.wt = wt_stores(a.D);
     if (a.N < 1 || a.N > AM_MAXN || a.T < 1 || a.T > kMergeMaxTables) return hipErrorInvalidValue;
     if (a.N > 1 && !a.pos) return hipErrorInvalidValue;
     const bool fwd = a.fwd_idx != nullptr;

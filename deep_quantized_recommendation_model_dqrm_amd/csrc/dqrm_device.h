@@ -112,11 +112,29 @@ DQRM_INLINE float4 ld4_wt(const float* p) {
     return make_float4(__uint_as_float((uint32_t)lo), __uint_as_float((uint32_t)(lo >> 32)),
                        __uint_as_float((uint32_t)hi), __uint_as_float((uint32_t)(hi >> 32)));
 }
-// 16-B write-through store (global_store_dwordx4 ... sc1)
+// 16-B write-through store (global_store_dwordx4 ... sc1). The compiler neither counts an asm
+// store in its s_waitcnt bookkeeping (its later vmcnt(N) waits then cover this store as well:
+// never too short, since vmcnt retires in issue order) nor pads the hazard behind it: the
+// s_nop 1 keeps the next instruction from overwriting the data registers before a store of
+// more than 8 bytes has read them.
 DQRM_INLINE void st4_wt(float4* p, float4 v) {
     typedef float v4f __attribute__((ext_vector_type(4)));
     const v4f x = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(x) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+}
+// Which once-written streams go write-through (DQRM_WT_STORES, dqrm_internal::wt_stores(); the
+// host passes the bits to the kernels in their arguments)
+constexpr uint32_t WT_Y = 1u;     // the forwards' output y
+constexpr uint32_t WT_HAND = 2u;  // the N > 1 hand-over buffers (coalesce workspace, payload)
+// 16 bytes of a streamed output: written once, not read again by the launch. A plain store
+// leaves the line dirty in the XCD's L2, and the kernel's end then writes every such byte back
+// before a dependent launch starts (MI355X_MICROARCH.md, price table row "boundary": 1.45 us +
+// dirty bytes / 6 TB/s). An sc1 store writes the line through and drops it ("inter-workgroup
+// visibility", stores of each flavour: 16-B sc1 ~ plain; row "publish-large": write-through wins
+// at tens of KB per workgroup). Whole 16-B stores only: 4- and 8-B sc1 stores are one fabric
+// write each, 3-12x the time per byte.
+DQRM_INLINE void st4_out(float4* p, float4 v, bool wt) {
+    if (wt) st4_wt(p, v); else *p = v;
 }
 // W stores of a narrow table (<= 256 rows: finalize rebuilds its maxima from W) go write-through
 DQRM_INLINE void st4_w(float4* p, float4 v, bool wt) {

@@ -97,7 +97,8 @@ __global__ void __launch_bounds__(QP_TPB) k_qpack(dqrm_internal::QuantPackArgs a
     auto emit = [&](int u, float4 x, int32_t r) {
         if (sub == 0) prow[u] = r;
         if (!quant) {
-            reinterpret_cast<float4*>(pval + (int64_t)u * D * 4)[sub] = x;
+            // (the quantized values are 4- or 8-B stores per lane: they stay plain)
+            st4_out(reinterpret_cast<float4*>(pval + (int64_t)u * D * 4) + sub, x, (a.wt & WT_HAND) != 0);
             return;
         }
         const float q0 = fake_quant(x.x, rr, qlo, qhi), q1 = fake_quant(x.y, rr, qlo, qhi);
@@ -136,7 +137,9 @@ __global__ void __launch_bounds__(QP_TPB) k_qpack(dqrm_internal::QuantPackArgs a
 
 namespace dqrm_internal {
 
-hipError_t launch_quant_pack(const QuantPackArgs& a, hipStream_t stream) {
+hipError_t launch_quant_pack(const QuantPackArgs& a0, hipStream_t stream) {
+    QuantPackArgs a = a0;
+    a.wt = wt_stores(a.D);
     // chunks per slot: the payload capacity spread evenly over the slots (a Criteo batch's
     // rows land roughly evenly in a table's row ranges), at least 1, at most 16
     const int64_t slots = (int64_t)a.T * SPLIT;

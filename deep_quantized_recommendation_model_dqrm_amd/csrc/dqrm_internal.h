@@ -23,6 +23,14 @@ DQRM_HIDDEN __attribute__((format(printf, 2, 3))) int set_error(int code, const 
             return dqrm_internal::set_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
     } while (0)
 
+// Which once-written streams the kernels store write-through (16-B sc1 stores, dqrm_device.h
+// st4_out): bits WT_Y / WT_HAND. DQRM_WT_STORES=0|y|hand|all in the environment (A/B), read
+// once per process (dqrm_kernels.hip); the launchers pass it on as a kernel argument or pick
+// the kernel instance by it. dim: the tables' row length -- y rows under 128 B (D < 32) stay
+// plain whatever the switch says: a 64-B row is half an L2 line, and written through it lost
+// (Kaggle, D = 16: 27.36 vs 27.03 us per step).
+DQRM_HIDDEN uint32_t wt_stores(int dim);
+
 // dqrm_linear.hip: what every dqrm_linear_* export rejects in a layer (quantized: the integer
 // buffers and bit widths as well) and in an activation code. Texts are "<who>: <fault>".
 DQRM_HIDDEN int check_linear(const dqrm_linear* l, int quantized, const char* who);
@@ -145,6 +153,7 @@ struct QuantPackArgs {
     int64_t cap_total;
     float* s_avg;                // [T]
     unsigned char* payload;
+    uint32_t wt;                 // wt_stores() bits (WT_HAND: the payload values write-through)
 };
 hipError_t launch_quant_pack(const QuantPackArgs& a, hipStream_t stream);
 
@@ -248,6 +257,7 @@ struct MergeApplyArgs {
     uint32_t fwd_flags;
     int fwd_gx;
     uint32_t spin_limit;              // gate polls before a forward workgroup flags DQRM_ERRF_STALL
+    uint32_t wt;                      // wt_stores() bits (WT_Y: y write-through)
     int diag;                         // DQRM_MERGE_DIAG (timing experiments only; 0 in normal use)
 };
 hipError_t launch_apply_merge(const MergeApplyArgs& a, hipStream_t stream);

@@ -69,6 +69,22 @@ int dqrm_internal::set_error(int code, const char* fmt, ...) {
     return code;
 }
 
+// DQRM_WT_STORES=0|y|hand|all (A/B): none / the forwards' y / the N > 1 hand-over buffers / both.
+// Unset or anything else: the default, y ("write-through stores of once-written
+// outputs": the hand-over buffers gained on the forced-collectives line only and moved no
+// WRITE_SIZE, the wide tables' W rows did not gain and are not in the code).
+uint32_t dqrm_internal::wt_stores(int dim) {
+    static const uint32_t v = [] {
+        const char* e = getenv("DQRM_WT_STORES");
+        if (e && !strcmp(e, "0")) return 0u;
+        if (e && !strcmp(e, "y")) return WT_Y;
+        if (e && !strcmp(e, "hand")) return WT_HAND;
+        if (e && !strcmp(e, "all")) return WT_Y | WT_HAND;
+        return WT_Y;
+    }();
+    return dim * (int)sizeof(float) >= 128 ? v : v & ~WT_Y;  // y rows of whole L2 lines only
+}
+
 namespace {
 
 using dqrm_internal::set_error;
@@ -241,6 +257,7 @@ struct FwdArgs {
     int pool1;  // DQRM_BATCH_POOLING_ONE: bag b of every table is lookup b (offsets unread)
     uint32_t* sync;     // k_finalize_fwd: the tables' sync words (gate, arrivals)
     uint32_t spin;      //   gate polls before a forward workgroup flags a stall
+    uint32_t wt;        // wt_stores() bits (WT_Y: out is stored write-through, st4_out)
 };
 
 // k_finalize_fwd's per-table sync words (apart from the merge apply's 8/9 and the one-launch
@@ -296,6 +313,7 @@ __device__ __forceinline__ void emb_fwd_table(const FwdArgs& a, int t, int64_t b
     const int lane = threadIdx.x % LPR;
     const int grp = threadIdx.x / LPR;
     const int D = LPR * 4;
+    const bool wty = (a.wt & WT_Y) != 0;
 
     // Every global load of a phase is issued unconditionally (addresses clamped into the
     // arrays, the values of invalid bags / lookups dropped afterwards), so the UNR bags' index
@@ -377,7 +395,11 @@ __device__ __forceinline__ void emb_fwd_table(const FwdArgs& a, int t, int64_t b
             waited = passed = true;
             take_scale();
         }
-        // phase 4: pooled sums for multi-lookup bags (bag order, FP32), quantize, store
+        // phase 4: pooled sums for multi-lookup bags (bag order, FP32), quantize; then the stores,
+        // together: the compiler does not count an asm store (st4_wt), so its wait for a later
+        // bag's row would cover the stores issued before it (vmcnt retires in issue order). A
+        // bag's output takes the place of its row in acc. (One compute loop for both store
+        // flavours: a copy per flavour cost 12-15 VGPRs, two waves per SIMD.)
 #pragma unroll
         for (int k = 0; k < UNR; ++k) {
             if (len[k] < 0) continue;
@@ -411,8 +433,16 @@ __device__ __forceinline__ void emb_fwd_table(const FwdArgs& a, int t, int64_t b
                     y.w = fake_quant(v.w, r, qlo, qhi) * s;
                 }
             }
-            const int64_t b = b0 + k * G + grp;
-            reinterpret_cast<float4*>(out + b * a.ost_b)[lane] = y;
+            acc[k] = y;
+        }
+        if (wty) {
+#pragma unroll
+            for (int k = 0; k < UNR; ++k)
+                if (len[k] >= 0) st4_wt(reinterpret_cast<float4*>(out + (b0 + k * G + grp) * a.ost_b) + lane, acc[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < UNR; ++k)
+                if (len[k] >= 0) reinterpret_cast<float4*>(out + (b0 + k * G + grp) * a.ost_b)[lane] = acc[k];
         }
     }
     if constexpr (GATE) {
@@ -467,6 +497,7 @@ __global__ void __launch_bounds__(256) k_emb_fwd_packed(FwdArgs a) {
     const int64_t* __restrict__ idx = a.idx + ibase;
     float* __restrict__ out = a.out + (int64_t)t * a.ost_t;
     const int tid = threadIdx.x;
+    const bool wty = (a.wt & WT_Y) != 0;
 
     for (int64_t b0 = (int64_t)blockIdx.x * 256; b0 < B; b0 += (int64_t)gridDim.x * 256) {
         // phase 1: one bag per thread
@@ -556,7 +587,7 @@ __global__ void __launch_bounds__(256) k_emb_fwd_packed(FwdArgs a) {
                 v4f yv = {y.x, y.y, y.z, y.w};
                 __builtin_nontemporal_store(yv, reinterpret_cast<v4f*>(dst));
             } else {
-                *dst = y;
+                st4_out(dst, y, wty);
             }
         }
     }
@@ -2733,6 +2764,7 @@ struct FArgs {
     float* fwd_scale;
     int fwd_bits;
     uint32_t fwd_flags;
+    uint32_t wt;        // wt_stores() bits (WT_Y: fwd_out is stored write-through, st4_out)
 };
 
 // workspace: the spill regions, only when a slot can exceed the in-LDS key capacity
@@ -3484,10 +3516,7 @@ __global__ void __launch_bounds__(SG_TPB) k_sgd_small(FArgs a) {
                                  : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             float* outt = a.fwd_out + (int64_t)t * a.fwd_ost_t;
-#pragma unroll
-            for (int k = 0; k < NPG; ++k) {
-                const int i = grp + k * G;
-                if (i >= B) continue;
+            auto row_out = [&](int k) -> float4 {
                 const bool ok = nxr[k] >= 0 && nxr[k] < nrows;
                 if (!ok && sub == 0) flag_error(a.err, DQRM_ERRF_INDEX);
                 float4 y = ok ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -3497,7 +3526,24 @@ __global__ void __launch_bounds__(SG_TPB) k_sgd_small(FArgs a) {
                     y.z = fake_quant(y.z, rf, qlo, qhi) * sf;
                     y.w = fake_quant(y.w, rf, qlo, qhi) * sf;
                 }
-                reinterpret_cast<float4*>(outt + (int64_t)i * a.fwd_ost_b)[sub] = y;
+                return y;
+            };
+            if ((a.wt & WT_Y) != 0) {
+                // write-through: every row quantized before the first store (a wait for a row must
+                // not cover an asm store the compiler does not count: st4_wt)
+#pragma unroll
+                for (int k = 0; k < NPG; ++k)
+                    if (grp + k * G < B) v[k] = row_out(k);
+#pragma unroll
+                for (int k = 0; k < NPG; ++k)
+                    if (grp + k * G < B) st4_wt(reinterpret_cast<float4*>(outt + (int64_t)(grp + k * G) * a.fwd_ost_b) + sub, v[k]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < NPG; ++k) {
+                    const int i = grp + k * G;
+                    if (i >= B) continue;
+                    reinterpret_cast<float4*>(outt + (int64_t)i * a.fwd_ost_b)[sub] = row_out(k);
+                }
             }
         }
     };
@@ -4313,6 +4359,7 @@ int launch_bwd(const BwdCall& c, hipStream_t st, const char* who) {
             if (fwd) {
                 fa.fwd_idx = c.next->idx; fa.fwd_out = c.fwd_out; fa.fwd_ost_t = c.fwd_ost_t; fa.fwd_ost_b = c.fwd_ost_b;
                 fa.fwd_scale = set->scale; fa.fwd_bits = c.fwd_bits; fa.fwd_flags = c.fwd_flags;
+                fa.wt = dqrm_internal::wt_stores(D);
             }
             DISPATCH_LPR(D, {
                 if (fwd) {
@@ -4452,6 +4499,7 @@ static int fwd_args(const dqrm_table_set* set, const dqrm_batch* batch, int bits
     a->pool1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
     a->out = out; a->B = batch->num_bags; a->ost_t = out_stride_t; a->ost_b = out_stride_b;
     a->T = set->num_tables; a->bits = bits; a->flags = flags;
+    a->wt = dqrm_internal::wt_stores(set->dim);
     return DQRM_OK;
 }
 
@@ -4469,6 +4517,12 @@ int dqrm_emb_fwd(const dqrm_table_set* set, const dqrm_batch* batch, int bits, u
         const int64_t cap = (16384 + a.T - 1) / a.T;
         if (bx > cap) bx = cap;
         const bool nt = (flags & DQRM_FWD_NT_STORE) != 0;
+        // y goes write-through only while the eight XCD L2s (32 MB) could hold all of it dirty at
+        // the kernel's end. A larger output is evicted as the kernel runs, the end's write-back
+        // is bounded by L2's size whatever the store, and the plain stream is what the 436 MB
+        // int4_gather line was tuned and measured with: kept. (The cut-off is reasoned; a
+        // write-through run of that line was not made.)
+        if ((int64_t)a.T * a.B * D * (int64_t)sizeof(float) > (32ll << 20)) a.wt &= ~WT_Y;
         DISPATCH_LPR(D, {
             if constexpr (LPR >= 2) {
                 if (nt)
