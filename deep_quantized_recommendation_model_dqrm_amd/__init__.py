@@ -21,6 +21,9 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers
   * ``quantized_ops.ops.quantized.embedding_bag_{4bit,byte}_*``  (row-wise PTQ inference formats)
+  * ``DLRM_Net.quantize_embedding`` and the quantized ``apply_emb`` (``DQRMNet.quantize_embedding`` /
+                                                                ``RowwiseTableSet``: all tables' row-wise
+                                                                bags in one launch, the FP32 slab optional)
 backed by hand-written HIP kernels behind the C ABI in ``include/dqrm.h`` (libdqrm.so).
 """
 from . import _lib
@@ -35,6 +38,7 @@ from .act import QuantAct
 from .mlp import FusedActivation, MLPStack, apply_mlp, create_mlp, fuse_activations, unfuse_activations
 from .interaction import DotInteraction, interact_features
 from .loss import DLRMLoss, loss_fn_wrap
+from .rowwise import RowwiseTableSet
 from .model import DQRMNet
 from .metrics import DLRMMetrics
 from . import quantized_ops
@@ -68,6 +72,7 @@ __all__ = [
     "DLRMLoss",
     "loss_fn_wrap",
     "DQRMNet",
+    "RowwiseTableSet",
     "DLRMMetrics",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",

@@ -157,6 +157,11 @@ EXPORTED_SYMBOLS = (
     "dqrm_rowwise_row_bytes",
     "dqrm_rowwise_prepack",
     "dqrm_rowwise_bag",
+    "dqrm_rowwise_set_fwd",
+    "dqrm_model_fwd_rowwise",
+    "dqrm_model_fwd_rowwise_workspace_bytes",
+    "dqrm_model_fwd_rowwise_workspace_layout",
+    "dqrm_model_fwd_rowwise_launches",
     "dqrm_init_uniform",
     "dqrm_checksum64",
     "dqrm_replica_mean",
@@ -330,6 +335,21 @@ class ModelLayout(C.Structure):
     _fields_ = [(name, C.c_size_t) for name in ("slab", "r", "p", "dr", "dx", "demb", "total")]
 
 
+class RowwiseSet(C.Structure):
+    """Mirror of ``dqrm_rowwise_set`` (include/dqrm.h): all tables' row-wise packed rows in one slab."""
+
+    _fields_ = [
+        ("num_tables", C.c_int32),
+        ("dim", C.c_int32),
+        ("bits", C.c_int32),
+        ("reserved", C.c_int32),
+        ("total_rows", C.c_int64),
+        ("packed", C.c_void_p),
+        ("meta", C.c_void_p),
+        ("err", C.c_void_p),
+    ]
+
+
 class Metrics(C.Structure):
     """Mirror of ``dqrm_metrics`` (include/dqrm.h)."""
 
@@ -405,6 +425,7 @@ def load(path: str | None = None) -> C.CDLL:
     PP = C.POINTER(C.c_void_p)  # a host array of device pointers
     MO = C.POINTER(Model)
     MS = C.POINTER(ML)  # a host array of stacks
+    RS = C.POINTER(RowwiseSet)
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
         "dqrm_refresh_scale_and_pack": (C.c_int, [TS, C.c_int, P]),
@@ -529,6 +550,11 @@ def load(path: str | None = None) -> C.CDLL:
             C.c_int,
             [C.c_int, P, C.c_int64, C.c_int, P, C.c_int64, P, C.c_int64, C.c_int, P, P, P, P],
         ),
+        "dqrm_rowwise_set_fwd": (C.c_int, [RS, BA, P, P, C.c_int64, C.c_int64, P]),
+        "dqrm_model_fwd_rowwise": (C.c_int, [MO, RS, BA, C.c_uint32, P, P, P, P, P, C.c_size_t, P]),
+        "dqrm_model_fwd_rowwise_workspace_bytes": (C.c_size_t, [MO, RS, C.c_int64]),
+        "dqrm_model_fwd_rowwise_workspace_layout": (C.c_int, [MO, RS, C.c_int64, C.POINTER(ModelLayout)]),
+        "dqrm_model_fwd_rowwise_launches": (C.c_int, [MO, RS, BA, C.c_uint32, C.c_int]),
         "dqrm_init_uniform": (C.c_int, [TS, C.c_uint64, P]),
         "dqrm_checksum64": (C.c_int, [P, C.c_int64, P, P]),
         "dqrm_replica_mean": (C.c_int, [P, C.c_int64, C.c_int, C.c_float, P]),

@@ -53,6 +53,12 @@ DQRM_HIDDEN int emb_check(const dqrm_table_set* set, const dqrm_batch* batch, co
 DQRM_HIDDEN int emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
                                      uint32_t fwd_flags);
 
+// dqrm_rowwise.hip, for dqrm_model_fwd_rowwise (dqrm_model.hip), which validates its embedding
+// stage before its first launch: everything dqrm_rowwise_set_fwd rejects in the set and (batch
+// nullable: the set alone) in the batch, apart from the out pointer and strides, which that caller
+// lays out itself.
+DQRM_HIDDEN int rowwise_set_check(const dqrm_rowwise_set* set, const dqrm_batch* batch, const char* who);
+
 // The coalesce backward of a Criteo-form batch (DQRM_BATCH_POOLING_ONE: table t's lookups
 // are idx[t*B, (t+1)*B), bag b = lookup b), written into the caller's coalesced-gradient
 // workspace (include/dqrm.h, dqrm_emb_bwd_coalesce).

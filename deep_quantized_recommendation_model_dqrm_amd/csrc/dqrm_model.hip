@@ -1,5 +1,6 @@
-// dqrm_model.hip — the whole DLRM per host call: dqrm_model_fwd (inference) and dqrm_model_step
-// (one training step at world size 1), gfx950.
+// dqrm_model.hip — the whole DLRM per host call: dqrm_model_fwd (inference), dqrm_model_step
+// (one training step at world size 1) and dqrm_model_fwd_rowwise (inference from the row-wise
+// INT4 / INT8 tables of DLRM_Net.quantize_embedding, :683-700, apply_emb :639-659), gfx950.
 //
 // Reference (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM @ 2024-10-24): DLRM_Net.forward /
 // sequential_forward (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:805-880: apply_mlp(bot_l),
@@ -27,21 +28,16 @@ constexpr int64_t kMaxB = (int64_t)1 << 20;  // dqrm_loss_fwd's one workgroup
 constexpr uint32_t kStepFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_REQUANT | DQRM_MODEL_NO_UPDATE | DQRM_MODEL_EMB_READY;
 constexpr uint32_t kFwdFlags = DQRM_MODEL_MLP_FRESH | DQRM_MODEL_EMB_READY;
 
-// the struct alone: members, every stage's own rules, and the widths between the stages
-int check_model(const dqrm_model* m, const char* what) {
-    if (!m) return set_error(DQRM_E_INVALID, "%s: null model", what);
-    if (!m->tables || !m->bottom || !m->top || !m->loss)
-        return set_error(DQRM_E_INVALID, "%s: null tables / bottom / top / loss", what);
-    int rc = emb_check(m->tables, nullptr, nullptr, m->embedding_bit, m->emb_fwd_flags, m->repack_bits, 0,
-                       what);
-    if (rc) return rc;
+// the stages behind the embedding (members not null) and the widths between all of them, for T
+// tables of dim D
+int check_stages(const dqrm_model* m, int T, int D, const char* what) {
+    int rc;
     if ((rc = check_mlp(m->bottom, what))) return rc;
     if ((rc = check_mlp(m->top, what))) return rc;
     const int Lb = m->bottom->num_layers, Lt = m->top->num_layers;
     if (Lb + Lt > DQRM_MLP_MAX_LAYERS)
         return set_error(DQRM_E_INVALID, "%s: bottom and top have %d layers in all, at most %d fit the update's launch",
                          what, Lb + Lt, DQRM_MLP_MAX_LAYERS);
-    const int T = m->tables->num_tables, D = m->tables->dim;
     const dqrm_interact* ic = &m->interact;
     if (ic->num_features != T + 1 || ic->dim != D)
         return set_error(DQRM_E_INVALID, "%s: interact needs num_features = tables + 1 = %d and dim = %d (got %d / %d)",
@@ -66,6 +62,27 @@ int check_model(const dqrm_model* m, const char* what) {
         return set_error(DQRM_E_INVALID, "%s: the top stack must return 1 feature (got %d)", what,
                          m->top->layers[Lt - 1].out_features);
     return DQRM_OK;
+}
+
+// the struct alone: members, every stage's own rules, and the widths between the stages
+int check_model(const dqrm_model* m, const char* what) {
+    if (!m) return set_error(DQRM_E_INVALID, "%s: null model", what);
+    if (!m->tables || !m->bottom || !m->top || !m->loss)
+        return set_error(DQRM_E_INVALID, "%s: null tables / bottom / top / loss", what);
+    int rc = emb_check(m->tables, nullptr, nullptr, m->embedding_bit, m->emb_fwd_flags, m->repack_bits, 0,
+                       what);
+    if (rc) return rc;
+    return check_stages(m, m->tables->num_tables, m->tables->dim, what);
+}
+
+// the row-wise forward's model: `tables` may be null and is never read, the set stands in for it
+int check_model_rowwise(const dqrm_model* m, const dqrm_rowwise_set* rset, const char* what) {
+    if (!m) return set_error(DQRM_E_INVALID, "%s: null model", what);
+    if (!m->bottom || !m->top || !m->loss)
+        return set_error(DQRM_E_INVALID, "%s: null bottom / top / loss", what);
+    int rc = rowwise_set_check(rset, nullptr, what);
+    if (rc) return rc;
+    return check_stages(m, rset->num_tables, rset->dim, what);
 }
 
 int check_B(int64_t B, const char* what) {
@@ -150,17 +167,20 @@ int wquant_launches(const dqrm_mlp* s) {
     return n;
 }
 
-// the forward both calls share; g == NULL and labels == NULL as dqrm_model_fwd passes them
-int run_forward(const dqrm_model* m, const dqrm_interact* ic, const dqrm_batch* batch, uint32_t flags, const float* x,
-                const float* labels, float* loss, float* z, float* g, char* w, const Cut& c, float* const* yb,
-                float* const* yt, void* stream) {
-    const int64_t B = batch->num_bags, T = m->tables->num_tables, D = m->tables->dim;
+// the forward all calls share; g == NULL and labels == NULL as dqrm_model_fwd passes them. rset:
+// the embedding stage is dqrm_rowwise_set_fwd over it, and m->tables is not read
+int run_forward(const dqrm_model* m, const dqrm_rowwise_set* rset, const dqrm_interact* ic, const dqrm_batch* batch,
+                uint32_t flags, const float* x, const float* labels, float* loss, float* z, float* g, char* w,
+                const Cut& c, float* const* yb, float* const* yt, void* stream) {
+    const int64_t B = batch->num_bags, T = ic->num_features - 1, D = ic->dim;
     const uint32_t mf = (flags & DQRM_MODEL_MLP_FRESH) ? DQRM_MLP_FRESH : 0;
     float* slab = (float*)(w + c.slab);
     float* r = (float*)(w + c.r);
     float* iscale = ic->quant_bits ? (float*)(w + c.iscale) : nullptr;
     int rc;
-    if (!(flags & DQRM_MODEL_EMB_READY) &&
+    if (rset) {
+        if ((rc = dqrm_rowwise_set_fwd(rset, batch, nullptr, slab, D, T * D, stream))) return rc;
+    } else if (!(flags & DQRM_MODEL_EMB_READY) &&
         (rc = dqrm_emb_fwd(m->tables, batch, m->embedding_bit, m->emb_fwd_flags, slab, D, T * D, stream)))
         return rc;
     if ((rc = dqrm_mlp_fwd(m->bottom, mf, x, B, yb, stream))) return rc;
@@ -179,9 +199,43 @@ void point_outputs(const dqrm_model* m, char* w, const Cut& c, float** yb, float
 
 dqrm_interact slab_interact(const dqrm_model* m) {
     dqrm_interact ic = m->interact;
-    ic.emb_stride_b = (int64_t)m->tables->num_tables * m->tables->dim;  // the [B][T][D] slab
-    ic.emb_stride_f = m->tables->dim;
+    ic.emb_stride_b = (int64_t)(ic.num_features - 1) * ic.dim;  // the [B][T][D] slab
+    ic.emb_stride_f = ic.dim;
     return ic;
+}
+
+// the row-wise forward's cut: the slab, the layers' outputs, r, the interaction's scale word and
+// the per-tensor layers' row maxima; nothing of the backward (model checked, B in range)
+void cut_workspace_fwd(const dqrm_model* m, int64_t B, Cut* c) {
+    const size_t T = m->interact.num_features - 1, D = m->interact.dim, f = sizeof(float), b = (size_t)B;
+    const size_t R = (size_t)m->top->layers[0].in_features;
+    *c = Cut{};
+    size_t at = 0;
+    c->slab = take(at, b * T * D * f);
+    for (int i = 0; i < m->bottom->num_layers; ++i) c->yb[i] = take(at, b * m->bottom->layers[i].out_features * f);
+    c->r = take(at, b * R * f);
+    for (int i = 0; i < m->top->num_layers; ++i) c->yt[i] = take(at, b * m->top->layers[i].out_features * f);
+    c->iscale = take(at, f);
+    const dqrm_mlp* both[2] = {m->bottom, m->top};
+    c->rowmax_bytes = dqrm_mlp_sgd_multi_workspace_bytes(both, 2);
+    c->rowmax = take(at, c->rowmax_bytes);
+    c->total = at;
+}
+
+// everything about a row-wise forward but its tensors and workspace
+int check_call_rowwise(const dqrm_model* m, const dqrm_rowwise_set* rset, const dqrm_batch* batch, uint32_t flags,
+                       const char* what) {
+    int rc = check_model_rowwise(m, rset, what);
+    if (rc) return rc;
+    if (flags & ~DQRM_MODEL_MLP_FRESH) return set_error(DQRM_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+    if (!batch) return set_error(DQRM_E_INVALID, "%s: null batch", what);
+    if ((rc = rowwise_set_check(rset, batch, what))) return rc;
+    if ((rc = check_B(batch->num_bags, what))) return rc;
+    // the interaction's piece index (dqrm_interact.hip's check_batch)
+    if (batch->num_bags > (int64_t)INT32_MAX / ((int64_t)m->interact.num_features * (m->interact.dim / 4)))
+        return set_error(DQRM_E_CAPACITY, "%s: B * num_features * dim / 4 exceeds 2^31 - 1 (B = %lld)", what,
+                         (long long)batch->num_bags);
+    return DQRM_OK;
 }
 
 }  // namespace
@@ -226,7 +280,7 @@ int dqrm_model_fwd(const dqrm_model* m, const dqrm_batch* batch, uint32_t flags,
     float *yb[DQRM_MLP_MAX_LAYERS], *yt[DQRM_MLP_MAX_LAYERS];
     point_outputs(m, w, c, yb, yt);
     const dqrm_interact ic = slab_interact(m);
-    return run_forward(m, &ic, batch, flags, x, labels, loss, z, nullptr, w, c, yb, yt, stream);
+    return run_forward(m, nullptr, &ic, batch, flags, x, labels, loss, z, nullptr, w, c, yb, yt, stream);
 }
 
 int dqrm_model_step(const dqrm_model* m, const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags,
@@ -247,7 +301,7 @@ int dqrm_model_step(const dqrm_model* m, const dqrm_batch* batch, const dqrm_bat
     float *yb[DQRM_MLP_MAX_LAYERS], *yt[DQRM_MLP_MAX_LAYERS];
     point_outputs(m, w, c, yb, yt);
     const dqrm_interact ic = slab_interact(m);
-    if ((rc = run_forward(m, &ic, batch, flags, x, labels, loss, z, g, w, c, yb, yt, stream))) return rc;
+    if ((rc = run_forward(m, nullptr, &ic, batch, flags, x, labels, loss, z, g, w, c, yb, yt, stream))) return rc;
 
     const int64_t B = batch->num_bags, T = m->tables->num_tables, D = m->tables->dim;
     float* slab = (float*)(w + c.slab);
@@ -289,6 +343,59 @@ int dqrm_model_step_launches(const dqrm_model* m, const dqrm_batch* batch, const
     if (flags & DQRM_MODEL_NO_UPDATE) return n;
     n += emb_bwd_sgd_launches(m->tables, batch, next, m->emb_fwd_flags);
     n += 1 + ((flags & DQRM_MODEL_REQUANT) && (has_tensor_layer(m->bottom) || has_tensor_layer(m->top)) ? 1 : 0);
+    return n;
+}
+
+int dqrm_model_fwd_rowwise_workspace_layout(const dqrm_model* m, const dqrm_rowwise_set* rset, int64_t B,
+                                            dqrm_model_layout* out) {
+    const char* what = "dqrm_model_fwd_rowwise_workspace_layout";
+    int rc = check_model_rowwise(m, rset, what);
+    if (rc) return rc;
+    if ((rc = check_B(B, what))) return rc;
+    if (!out) return set_error(DQRM_E_INVALID, "%s: null out", what);
+    Cut c;
+    cut_workspace_fwd(m, B, &c);
+    *out = dqrm_model_layout{};
+    out->slab = c.slab;
+    out->r = c.r;
+    out->p = c.yt[m->top->num_layers - 1];
+    out->total = c.total;
+    return DQRM_OK;
+}
+
+size_t dqrm_model_fwd_rowwise_workspace_bytes(const dqrm_model* m, const dqrm_rowwise_set* rset, int64_t B) {
+    dqrm_model_layout l;
+    return dqrm_model_fwd_rowwise_workspace_layout(m, rset, B, &l) ? 0 : l.total;
+}
+
+int dqrm_model_fwd_rowwise(const dqrm_model* m, const dqrm_rowwise_set* rset, const dqrm_batch* batch, uint32_t flags,
+                           const float* x, const float* labels, float* loss, float* z, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    const char* what = "dqrm_model_fwd_rowwise";
+    int rc = check_call_rowwise(m, rset, batch, flags, what);
+    if (rc) return rc;
+    if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);
+    if (labels && !loss) return set_error(DQRM_E_INVALID, "%s: labels need a loss to write (null loss)", what);
+    Cut c;
+    cut_workspace_fwd(m, batch->num_bags, &c);
+    if ((rc = check_workspace(c, workspace, workspace_bytes, what))) return rc;
+    char* w = (char*)workspace;
+    float *yb[DQRM_MLP_MAX_LAYERS], *yt[DQRM_MLP_MAX_LAYERS];
+    point_outputs(m, w, c, yb, yt);
+    const dqrm_interact ic = slab_interact(m);
+    return run_forward(m, rset, &ic, batch, flags, x, labels, loss, z, nullptr, w, c, yb, yt, stream);
+}
+
+int dqrm_model_fwd_rowwise_launches(const dqrm_model* m, const dqrm_rowwise_set* rset, const dqrm_batch* batch,
+                                    uint32_t flags, int has_labels) {
+    const char* what = "dqrm_model_fwd_rowwise_launches";
+    int rc = check_call_rowwise(m, rset, batch, flags, what);
+    if (rc) return rc;
+    int n = 1;                                                          // dqrm_rowwise_set_fwd
+    n += m->bottom->num_layers + m->top->num_layers;                    // the stacks' forwards
+    if (!(flags & DQRM_MODEL_MLP_FRESH)) n += wquant_launches(m->bottom) + wquant_launches(m->top);
+    n += (m->interact.quant_bits ? 1 : 0) + 1;                          // dqrm_interact_scale, _fwd
+    n += has_labels ? 1 : 0;                                            // dqrm_loss_fwd
     return n;
 }
 

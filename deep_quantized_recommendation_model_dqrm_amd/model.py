@@ -13,6 +13,11 @@ a ``DLRMLoss``.
     one ABI crossing: no autograd graph, no per-stage tensors, no optimizer. The library calls the
     stages' own exports in the composition's order, so every buffer holds the composition's bits.
 
+  * ``quantize_embedding(bits)`` is the reference's ``DLRM_Net.quantize_embedding`` (:683-700): the
+    tables prepacked row-wise to INT4 / INT8 (``RowwiseTableSet``); ``predict`` and ``evaluate`` then
+    run from the packed rows (dqrm_model_fwd_rowwise: still one host call and one embedding launch
+    per batch) and the FP32 slab may be released.
+
 A model is built on its GPU (``device=``) and stays there; there is no CPU path.
 
 World size > 1 is out of scope of ``train_step``'s update: use ``train_step(..., update=False)``,
@@ -31,7 +36,8 @@ from . import _lib as L
 from .interaction import DotInteraction, out_features
 from .loss import DLRMLoss
 from .mlp import MLPStack, _on_device, create_mlp
-from .quant_modules_not_quantize_grad import error_check_due, poll_device_errors
+from .quant_modules_not_quantize_grad import error_check_due, poll_device_errors, raise_device_errors
+from .rowwise import RowwiseTableSet
 from .tables import EmbeddingTableSet, LookupBatch, _stream_handle
 
 
@@ -67,6 +73,14 @@ class DQRMNet(nn.Module):
     its own embedding forward only if its ``batch`` is that very object, the batch size is the
     same and no table write went through ``model.tables``'s methods or this
     model's other calls in between; otherwise it runs the forward itself.
+
+    Quantized serving. After ``quantize_embedding(bits)`` (4 or 8) ``quantize_emb`` is True,
+    ``quantize_bits`` is ``bits`` and ``emb_q`` the ``RowwiseTableSet``; ``predict`` / ``evaluate`` read
+    it (no fake-quant on top, as the reference's ``apply_emb`` :639-659), ``forward`` and
+    ``train_step`` raise ``RuntimeError`` (the reference's ``emb_l`` is ``None`` there).
+    ``keep_fp32=True`` keeps the untouched FP32 tables, and ``dequantize_embedding()`` returns to
+    them; ``keep_fp32=False`` releases them: ``tables`` is None and the ``emb_weight`` buffer gives
+    way to ``emb_packed``, the packed slab, in ``state_dict()``.
 
     Not built: ``quantize_activation`` (``MLPStack`` does not run those layers), momentum, weight
     decay, world size > 1 inside the step."""
@@ -130,7 +144,12 @@ class DQRMNet(nn.Module):
         self.emb_out = None    # forward(): the embedding slab [B, T, D], a leaf whose .grad is demb
         self.z = None          # train_step(): the clamped prediction [B, 1]
         self.emb_grad = None   # train_step(update=False): demb [B, T, D], a view of the workspace
+        self.quantize_emb = False  # quantize_embedding(): predict / evaluate read emb_q
+        self.quantize_bits = None  #   its bits, 4 or 8 (the interaction's are interact.quantize_bits)
+        self.emb_q = None          #   the RowwiseTableSet
         d = self.__dict__      # plain attributes of the step (nn.Module.__setattr__ is slow per call)
+        d["_ws_q"] = None      # (tensor, B): the row-wise forward's workspace, its own high-water mark
+        d["_lay_q"] = None     # (L.Model, B, L.ModelLayout)
         d["_ws"] = None        # (tensor, B, max_lookups): the workspace's high-water mark
         d["_cm"] = None        # (key, L.Model, what it points into)
         d["_out"] = None       # (B, z, g)
@@ -141,6 +160,11 @@ class DQRMNet(nn.Module):
 
     # ------------------------------------------------------------ bookkeeping
     def _device(self, what):
+        if self.tables is None and self.emb_q is not None:  # quantize_embedding(keep_fp32=False)
+            if self.emb_packed.data_ptr() != self.emb_q.packed.data_ptr():
+                raise L.DQRMError("DQRMNet was moved or cast after quantize_embedding: its packed tables live "
+                                  "in the RowwiseTableSet's slab")
+            return self.emb_packed.device
         dev = self.emb_weight.device
         if self.tables is None or dev.type != "cuda":
             raise _no_cpu(what, dev)
@@ -162,6 +186,10 @@ class DQRMNet(nn.Module):
         if self.tables is not None:
             self._device("load_state_dict")
             self.tables.refresh_absmax()  # W changed outside the kernels: rebuild the |W| hierarchy
+            if self.emb_q is not None:    # ... and the packed rows derived from it
+                self.emb_q = RowwiseTableSet.from_tables(self.tables, self.quantize_bits)
+        elif self.emb_q is not None:
+            self._device("load_state_dict")
         self.invalidate()
         return out
 
@@ -172,8 +200,8 @@ class DQRMNet(nn.Module):
         dev = self._device(what)
         if not isinstance(batch, LookupBatch):
             raise TypeError(f"DQRMNet.{what} takes a LookupBatch")
-        if batch.num_tables != self.tables.T:
-            raise ValueError("batch has %d tables, set has %d" % (batch.num_tables, self.tables.T))
+        if batch.num_tables != len(self.ln_emb):
+            raise ValueError("batch has %d tables, set has %d" % (batch.num_tables, len(self.ln_emb)))
         B = batch.num_bags
         if (not isinstance(dense_x, torch.Tensor) or dense_x.dtype != torch.float32 or dense_x.device != dev
                 or tuple(dense_x.shape) != (B, self.ln_bot[0]) or not dense_x.is_contiguous()):
@@ -192,7 +220,8 @@ class DQRMNet(nn.Module):
         cb, ct = self.bot_stack._c_struct(kb), self.top_stack._c_struct(kt)
         loss = self.loss
         w = loss.loss_ws
-        key = (id(cb), id(ct), id(self.tables.c), loss.loss_function, loss.loss_threshold,
+        tc = None if self.tables is None else self.tables.c  # released: dqrm_model_fwd_rowwise reads no tables
+        key = (id(cb), id(ct), id(tc), loss.loss_function, loss.loss_threshold,
                None if w is None else w.data_ptr(), self.interact.arch_interaction_itself, self.interact._bits,
                self.embedding_bit, self.embedding_full_precision)
         ent = self.__dict__["_cm"]
@@ -200,18 +229,20 @@ class DQRMNet(nn.Module):
             return ent[1]
         lc = loss._config()
         m = L.Model()
-        m.tables, m.bottom, m.top, m.loss = C.pointer(self.tables.c), C.pointer(cb), C.pointer(ct), C.pointer(lc)
-        m.interact.num_features, m.interact.dim = self.tables.T + 1, self.tables.D
+        m.bottom, m.top, m.loss = C.pointer(cb), C.pointer(ct), C.pointer(lc)
+        if tc is not None:
+            m.tables = C.pointer(tc)
+        m.interact.num_features, m.interact.dim = len(self.ln_emb) + 1, self.m_spa
         m.interact.self_interaction = int(self.interact.arch_interaction_itself)
         m.interact.quant_bits = self.interact._bits
         m.embedding_bit, m.emb_fwd_flags = self.embedding_bit, self._fwd_flags()
         m.ste, m.repack_bits = int(not self.embedding_full_precision), 0
-        self.__dict__["_cm"] = (key, m, (cb, ct, lc, self.tables.c))
+        self.__dict__["_cm"] = (key, m, (cb, ct, lc, tc))
         return m
 
     def _prepare(self, what):
         """The stacks' checks, their keys and the model struct."""
-        if self.loss.loss_function == "wbce" and self.loss.loss_ws.device != self.emb_weight.device:
+        if self.loss.loss_function == "wbce" and self.loss.loss_ws.device != self._device(what):
             raise ValueError("DLRMLoss.loss_ws is not on the model's device")
         self.bot_stack._prepare()
         self.top_stack._prepare()
@@ -289,7 +320,101 @@ class DQRMNet(nn.Module):
 
     def _poll(self):
         if error_check_due(self) and not torch.cuda.is_current_stream_capturing():
-            poll_device_errors(self.tables)
+            poll_device_errors(self.tables if self.emb_q is None else self.emb_q)
+
+    def _not_quantized(self, what):
+        if self.emb_q is not None:
+            raise RuntimeError(f"DQRMNet.{what}: the model serves row-wise quantized tables after "
+                               "quantize_embedding() and cannot train (the reference's emb_l is None there); "
+                               "call dequantize_embedding() first (quantize_embedding(keep_fp32=True) allows it)")
+
+    # ------------------------------------------------------------ quantized serving
+    def quantize_embedding(self, bits, keep_fp32=True):
+        """The reference's ``DLRM_Net.quantize_embedding(bits)`` (:683-700): every table prepacked
+        row-wise to 4- or 8-bit rows by one launch over the slab; ``predict`` / ``evaluate`` then
+        gather from ``model.emb_q``. Any other ``bits`` raises ``ValueError`` (the reference prints
+        nothing and returns). keep_fp32=False releases the FP32 tables (see the class docstring).
+        Calling it again on a model that kept its FP32 tables repacks them with the new bits."""
+        if isinstance(bits, bool) or bits not in (4, 8):
+            raise ValueError(f"DQRMNet.quantize_embedding: bits must be 4 or 8, got {bits!r}")
+        if self.tables is None and self.emb_q is not None:
+            raise L.DQRMError("DQRMNet.quantize_embedding: the FP32 tables were released "
+                              "(quantize_embedding(keep_fp32=False)); there is nothing to pack again")
+        self._device("quantize_embedding")
+        q = RowwiseTableSet.from_tables(self.tables, int(bits))
+        self.emb_q, self.quantize_emb, self.quantize_bits = q, True, int(bits)
+        d = self.__dict__
+        d["_ws_q"] = d["_lay_q"] = None
+        if keep_fp32:  # the training workspace and its prefetch record stay as they are
+            return
+        del self.emb_weight
+        self.register_buffer("emb_packed", q.packed, persistent=True)  # the packed slab itself
+        self.tables = None
+        self.emb_out = self.emb_grad = None
+        d["_ws"] = d["_cm"] = d["_lay"] = d["_prefetched"] = None
+
+    def dequantize_embedding(self):
+        """Drop the packed tables of ``quantize_embedding(bits, keep_fp32=True)``: every path reads
+        the FP32 tables again, which were never modified."""
+        if self.emb_q is None:
+            return
+        if self.tables is None:
+            raise L.DQRMError("DQRMNet.dequantize_embedding: the FP32 tables were released "
+                              "(quantize_embedding(keep_fp32=False))")
+        self.emb_q, self.quantize_emb, self.quantize_bits = None, False, None
+        self.__dict__["_ws_q"] = self.__dict__["_lay_q"] = None
+
+    def _workspace_q(self, m, B, dev):
+        """The row-wise forward's own buffer (a forward-only cut), grown to the largest B seen."""
+        ent = self.__dict__["_ws_q"]
+        if ent is not None and ent[1] >= B and ent[0].device == dev:
+            return ent[0]
+        need = self.emb_q.lib.dqrm_model_fwd_rowwise_workspace_bytes(C.byref(m), C.byref(self.emb_q.c), B)
+        if need == 0:
+            L.check(L.DQRM_E_INVALID, "dqrm_model_fwd_rowwise_workspace_bytes")
+        ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        self.__dict__["_ws_q"] = (ws, B)
+        return ws
+
+    def _predict_q(self, dense_x, batch, labels, dev, B):
+        kb, kt, m = self._prepare("predict")
+        fresh = self.bot_stack.is_fresh(kb) and self.top_stack.is_fresh(kt)
+        q = self.emb_q
+        ws = self._workspace_q(m, B, dev)
+        self._poll()
+        loss = z = None
+        if labels is not None:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            z = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        L.check(q.lib.dqrm_model_fwd_rowwise(
+            C.byref(m), C.byref(q.c), C.byref(batch.c), L.DQRM_MODEL_MLP_FRESH if fresh else 0, dense_x.data_ptr(),
+            None if labels is None else labels.data_ptr(), None if loss is None else loss.data_ptr(),
+            None if z is None else z.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle()),
+            "dqrm_model_fwd_rowwise")
+        if labels is not None:
+            return loss, z
+        ent = self.__dict__["_lay_q"]
+        if ent is None or ent[0] is not m or ent[1] != B:
+            lay = L.ModelLayout()
+            L.check(q.lib.dqrm_model_fwd_rowwise_workspace_layout(C.byref(m), C.byref(q.c), B, C.byref(lay)),
+                    "dqrm_model_fwd_rowwise_workspace_layout")
+            ent = self.__dict__["_lay_q"] = (m, B, lay)
+        return ws[ent[2].p: ent[2].p + 4 * B].view(torch.float32).view(B, 1).clone()
+
+    def fwd_rowwise_launches(self, batch, labels=False, fresh=None):
+        """dqrm_model_fwd_rowwise_launches for a ``predict`` of the quantized model (fresh None: the
+        stacks' current state)."""
+        self._device("fwd_rowwise_launches")
+        if self.emb_q is None:
+            raise RuntimeError("DQRMNet.fwd_rowwise_launches: call quantize_embedding() first")
+        kb, kt, m = self._prepare("fwd_rowwise_launches")
+        if fresh is None:
+            fresh = self.bot_stack.is_fresh(kb) and self.top_stack.is_fresh(kt)
+        n = self.emb_q.lib.dqrm_model_fwd_rowwise_launches(C.byref(m), C.byref(self.emb_q.c), C.byref(batch.c),
+                                                           L.DQRM_MODEL_MLP_FRESH if fresh else 0, int(bool(labels)))
+        if n < 0:
+            L.check(n, "dqrm_model_fwd_rowwise_launches")
+        return n
 
     # ------------------------------------------------------------ the composition
     def forward(self, dense_x, batch):
@@ -297,6 +422,7 @@ class DQRMNet(nn.Module):
         stack as autograd nodes. ``model.emb_out`` is the embedding slab ``[B, T, D]``, a leaf: after
         ``backward()`` its ``.grad`` is what ``model.tables.backward_sgd(batch, grad, lr,
         layout="btd")`` takes; the stacks are updated with ``sgd_step``."""
+        self._not_quantized("forward")
         self._device("forward")
         x = self.bot_stack(dense_x)
         slab = self.tables.forward(batch, bits=self.embedding_bit, refresh_scale=True,
@@ -310,9 +436,11 @@ class DQRMNet(nn.Module):
     def predict(self, dense_x, batch, labels=None):
         """The forward as ONE host call (dqrm_model_fwd): p ``[B, 1]`` without labels, ``(E, Z)``
         with them: the 0-dim loss and the clamped prediction. Quantizes the MLP weights only when
-        the stacks are not fresh (``requantize()`` makes them so)."""
+        the stacks are not fresh (``requantize()`` makes them so). After ``quantize_embedding`` the
+        same, from the row-wise packed tables (dqrm_model_fwd_rowwise)."""
         dev, B = self._check_inputs(dense_x, batch, labels, "predict")
-        return _on_device(dev, self._predict, dense_x, batch, labels, dev, B)
+        return _on_device(dev, self._predict if self.emb_q is None else self._predict_q, dense_x, batch, labels,
+                          dev, B)
 
     def _predict(self, dense_x, batch, labels, dev, B):
         kb, kt, m = self._prepare("predict")
@@ -376,12 +504,16 @@ class DQRMNet(nn.Module):
             dev, B = self._check_inputs(dense_x, batch, labels, "evaluate")
             if metrics is None:
                 metrics = DLRMMetrics(max(nb, 1) * B, device=dev)
-            _, Z = _on_device(dev, self._predict, dense_x, batch, labels, dev, B)
+            _, Z = _on_device(dev, self._predict if self.emb_q is None else self._predict_q, dense_x, batch,
+                              labels, dev, B)
             metrics.update(Z, labels)
             seen += 1
         if seen == 0:
             raise ValueError("DQRMNet.evaluate: no batch given")
-        return metrics.compute()
+        out = metrics.compute()
+        if self.emb_q is not None:  # compute() has synchronised: one read of the packed set's flags
+            raise_device_errors(self.emb_q.read_errors(clear=True))
+        return out
 
     def requantize(self):
         """Quantize both stacks' weights now and mark them fresh (``MLPStack.requantize``)."""
@@ -392,6 +524,7 @@ class DQRMNet(nn.Module):
     def step_launches(self, batch, next_batch=None, update=True, prefetched=False, fresh=None):
         """dqrm_model_step_launches for a ``train_step`` with these arguments (fresh None: the
         stacks' current state)."""
+        self._not_quantized("step_launches")
         self._device("step_launches")
         kb, kt, m = self._prepare("step_launches")
         if fresh is None:
@@ -419,6 +552,7 @@ class DQRMNet(nn.Module):
 
         The MLP gradients are written into persistent tensors bound as ``p.grad`` (overwritten,
         not accumulated)."""
+        self._not_quantized("train_step")
         dev, B = self._check_inputs(dense_x, batch, labels, "train_step")
         if next_batch is not None:
             if not update:

@@ -91,7 +91,13 @@ extern "C" {
                                   likewise within 12: the test loop's metrics, dqrm_metrics
                                   (DLRMMetrics): dqrm_metrics_reset, dqrm_metrics_update,
                                   dqrm_metrics_workspace_bytes, dqrm_metrics_finish,
-                                  dqrm_metrics_finish_launches */
+                                  dqrm_metrics_finish_launches;
+                                  likewise within 12: the quantized model served from row-wise
+                                  tables, dqrm_rowwise_set (DQRMNet.quantize_embedding):
+                                  dqrm_rowwise_set_fwd, dqrm_model_fwd_rowwise,
+                                  dqrm_model_fwd_rowwise_workspace_bytes,
+                                  dqrm_model_fwd_rowwise_workspace_layout,
+                                  dqrm_model_fwd_rowwise_launches */
 
 /* status codes */
 #define DQRM_OK            0
@@ -1145,6 +1151,68 @@ int dqrm_rowwise_prepack(int bits, const float* W, int64_t num_rows, int dim, ui
 int dqrm_rowwise_bag(int bits, const uint8_t* packed, int64_t num_rows, int dim, const int64_t* idx,
                      int64_t num_lookups, const int64_t* off, int64_t num_bags, int include_last_offset,
                      const float* per_sample_weights, float* out, uint32_t* err, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The quantized model served from row-wise tables, csrc/dqrm_rowwise.hip and dqrm_model.hip.
+ * DLRM_Net.quantize_embedding(bits) (dlrm_s_pytorch_tb_dp_one_parallel_comm.py:683-700) prepacks
+ * every table and sets emb_l = None; apply_emb (:639-659) then gathers table after table with
+ * embedding_bag_{4bit,byte}_rowwise_offsets. Here all T packed tables are ONE slab
+ * u8 [total_rows][dqrm_rowwise_row_bytes(bits, dim)] in dqrm_rowwise_prepack's row layout, table t
+ * in rows [row_base[t], row_base[t] + num_rows[t]), and all tables' bags are one launch. (The FP32
+ * slab of a dqrm_table_set is [R][D] contiguous and prepacking is per row, so one
+ * dqrm_rowwise_prepack over its R rows packs every table.)
+ *
+ * The struct is HOST memory, its pointers device memory. meta: i64 [2][T], row_base then num_rows
+ * (the first two rows of dqrm_table_set.meta serve). err: one word of DQRM_ERRF_* flags, cleared by
+ * the caller. packed is 4-byte aligned.
+ * ------------------------------------------------------------------------------ */
+typedef struct dqrm_rowwise_set {
+    int32_t  num_tables;      /* T, 1..256 */
+    int32_t  dim;             /* D: 8, 16, 32, 64, 128 or 256 */
+    int32_t  bits;            /* 4 or 8 */
+    int32_t  reserved;
+    int64_t  total_rows;      /* R = sum num_rows */
+    const uint8_t* packed;    /* [R][row_bytes] */
+    const int64_t* meta;      /* [2][T]: row_base, num_rows */
+    uint32_t* err;            /* 1 word, device-side error flags */
+} dqrm_rowwise_set;
+
+/* apply_emb's loop over the quantized tables (:639-659) as ONE launch: out[t*out_stride_t +
+ * b*out_stride_b + d] (dqrm_emb_fwd's addressing) <- table t's bag b, dqrm_rowwise_bag's
+ * arithmetic and bits. batch in either form: DQRM_BATCH_POOLING_ONE (bag b is lookup b of
+ * idx[t*B, (t+1)*B); off and idx_base are not read and may be NULL) or idx_base / off[T][B] with
+ * the last bag ending at L_t. per_sample_weights: NULL or f32 [sum L_t], parallel to idx. An index
+ * outside [0, num_rows[t]) flags DQRM_ERRF_INDEX and contributes nothing; a bad offset pair flags
+ * DQRM_ERRF_OFFSET and is clamped as in dqrm_rowwise_bag; no address outside the arrays is formed.
+ * out 16-byte aligned, strides multiples of 4 floats. num_bags == 0: nothing is launched. */
+int dqrm_rowwise_set_fwd(const dqrm_rowwise_set* set, const dqrm_batch* batch, const float* per_sample_weights,
+                         float* out, int64_t out_stride_t, int64_t out_stride_b, void* stream);
+
+/* dqrm_model_fwd with the embedding stage replaced by dqrm_rowwise_set_fwd into the [B][T][D] slab:
+ * DLRM_Net.forward after quantize_embedding (:683-700; apply_emb :639-659 applies no fake-quant on
+ * top of the row-wise gather, so model->embedding_bit / emb_fwd_flags are ignored). model->tables
+ * may be NULL and is never read; rset->dim must be model->interact.dim and rset->num_tables + 1
+ * model->interact.num_features. flags: DQRM_MODEL_MLP_FRESH only. Everything else as
+ * dqrm_model_fwd: no arithmetic here, validated before the first launch, a rejected call writes
+ * nothing (DQRM_E_INVALID / DQRM_E_WORKSPACE as there), nothing allocated or synchronised.
+ *
+ * The workspace is a forward-only cut, dqrm_model_fwd_rowwise_workspace_bytes(model, rset, B)
+ * bytes (0 for arguments it rejects), 16-byte aligned: the slab (offset 0), every layer's output,
+ * r, the interaction's scale word and the per-tensor layers' row maxima, each on a 256-byte
+ * boundary; no dr / dx / demb and no backward scratch. _workspace_layout fills slab, r, p and
+ * total; dr, dx and demb are 0.
+ *
+ * dqrm_model_fwd_rowwise_launches: 1 (the embedding forward) + L (the stacks' layers) + 1 (the
+ * interaction) + 1 for the quantized interaction's scale + 1 with labels + dqrm_model_step_launches'
+ * additions when not fresh; <0 on arguments the call rejects (workspace and tensors apart). */
+int dqrm_model_fwd_rowwise(const dqrm_model* model, const dqrm_rowwise_set* rset, const dqrm_batch* batch,
+                           uint32_t flags, const float* x, const float* labels, float* loss, float* z,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t dqrm_model_fwd_rowwise_workspace_bytes(const dqrm_model* model, const dqrm_rowwise_set* rset, int64_t B);
+int dqrm_model_fwd_rowwise_workspace_layout(const dqrm_model* model, const dqrm_rowwise_set* rset, int64_t B,
+                                            dqrm_model_layout* out);
+int dqrm_model_fwd_rowwise_launches(const dqrm_model* model, const dqrm_rowwise_set* rset, const dqrm_batch* batch,
+                                    uint32_t flags, int has_labels);
 
 /* ---------------------------------------------------------------------------------
  * Criteo input path
