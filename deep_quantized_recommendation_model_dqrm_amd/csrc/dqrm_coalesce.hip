@@ -1870,53 +1870,14 @@ namespace dqrm_internal {
 
 int coalesce_apply_grid(int T) { return (T + 7) / 8 * 64; }
 
-void plan_table_groups(const int64_t* num_rows_host, int T, LocalApplyArgs* la);
-
-void plan_sub_slots(const int64_t* num_rows_host, int T, LocalApplyArgs* la) {
-    static const bool off = [] {
-        const char* e = getenv("DQRM_SUBSLOTS");
-        return e && !strcmp(e, "0");
-    }();
-    la->sub_mask = 0;
-    for (int e = 0; e < kSubTables; ++e) la->sub_table[e] = -1;
-    if (off || !num_rows_host || T <= 0 || T > kCoalesceApplyMaxT) return;
-    const int nextra = coalesce_apply_grid(T) / SPLIT - T;  // spare groups of 8 workgroups
-    // eligible: row-split tables of >= 16 row blocks (each half-slot keeps >= 1 block), by row
-    // blocks descending, ties by table index
-    int order[kCoalesceApplyMaxT];
-    int64_t nb[kCoalesceApplyMaxT];
-    int ne = 0;
-    for (int t = 0; t < T; ++t) {
-        nb[t] = (num_rows_host[t] + BLK - 1) / BLK;
-        if (nb[t] >= 2 * SPLIT) order[ne++] = t;
-    }
-    // DQRM_SUBSLOT_ORDER=small (A/B): the smallest eligible tables first (their slots hold
-    // duplicate-heavy lookups: sort, ordered sums, block re-reductions), not the largest
-    static const bool small_first = [] {
-        const char* e = getenv("DQRM_SUBSLOT_ORDER");
-        return e && !strcmp(e, "small");
-    }();
-    if (small_first) std::stable_sort(order, order + ne, [&](int x, int y) { return nb[x] < nb[y]; });
-    else std::stable_sort(order, order + ne, [&](int x, int y) { return nb[x] > nb[y]; });
-    for (int e = 0; e < nextra && e < ne && e < kSubTables; ++e) {
-        la->sub_table[e] = (int8_t)order[e];
-        la->sub_mask |= 1u << order[e];
-    }
-    plan_table_groups(num_rows_host, T, la);
-}
-
 // DQRM_TABLE_GROUPS=critical (A/B): the groups a table's 8 slots run in, XCD by XCD (group g's
 // workgroups share XCD g % 8), filled with the tables expected to end last first -- uneven
 // row-split slots (8 < blocks < 16, not a multiple of 8), then a few-row tables' long ordered
 // chains, then medium tables, the big distinct-row tables last
 void plan_table_groups(const int64_t* num_rows_host, int T, LocalApplyArgs* la) {
-    static const bool crit = [] {
-        const char* e = getenv("DQRM_TABLE_GROUPS");
-        return e && !strcmp(e, "critical");
-    }();
     la->group_perm = 0;
     for (int g = 0; g < kSubTables; ++g) la->table_of_group[g] = (int8_t)g;
-    if (!crit || !num_rows_host || T <= 0 || T > kCoalesceApplyMaxT) return;
+    if (!env_table_groups_critical() || !num_rows_host || T <= 0 || T > kCoalesceApplyMaxT) return;
     int score[kCoalesceApplyMaxT], tabs[kCoalesceApplyMaxT], groups[kCoalesceApplyMaxT];
     for (int t = 0; t < T; ++t) {
         const int64_t n = num_rows_host[t], nb = (n + BLK - 1) / BLK;
@@ -1929,6 +1890,31 @@ void plan_table_groups(const int64_t* num_rows_host, int T, LocalApplyArgs* la) 
         for (int g = x; g < T; g += SPLIT) groups[ng++] = g;
     for (int i = 0; i < T; ++i) la->table_of_group[groups[i]] = (int8_t)tabs[i];
     la->group_perm = 1;
+}
+
+void plan_sub_slots(const int64_t* num_rows_host, int T, LocalApplyArgs* la) {
+    la->sub_mask = 0;
+    for (int e = 0; e < kSubTables; ++e) la->sub_table[e] = -1;
+    if (!env_subslots() || !num_rows_host || T <= 0 || T > kCoalesceApplyMaxT) return;
+    const int nextra = coalesce_apply_grid(T) / SPLIT - T;  // spare groups of 8 workgroups
+    // eligible: row-split tables of >= 16 row blocks (each half-slot keeps >= 1 block), by row
+    // blocks descending, ties by table index
+    int order[kCoalesceApplyMaxT];
+    int64_t nb[kCoalesceApplyMaxT];
+    int ne = 0;
+    for (int t = 0; t < T; ++t) {
+        nb[t] = (num_rows_host[t] + BLK - 1) / BLK;
+        if (nb[t] >= 2 * SPLIT) order[ne++] = t;
+    }
+    // DQRM_SUBSLOT_ORDER=small (A/B): the smallest eligible tables first (their slots hold
+    // duplicate-heavy lookups: sort, ordered sums, block re-reductions), not the largest
+    if (env_subslot_small_first()) std::stable_sort(order, order + ne, [&](int x, int y) { return nb[x] < nb[y]; });
+    else std::stable_sort(order, order + ne, [&](int x, int y) { return nb[x] > nb[y]; });
+    for (int e = 0; e < nextra && e < ne && e < kSubTables; ++e) {
+        la->sub_table[e] = (int8_t)order[e];
+        la->sub_mask |= 1u << order[e];
+    }
+    plan_table_groups(num_rows_host, T, la);
 }
 
 bool coalesce_apply_resident(int T, hipStream_t stream) {
@@ -1981,12 +1967,8 @@ hipError_t launch_coalesce_pool1(const CoalesceArgs& a, const LocalApplyArgs* la
     const bool rm = DQRM_COAL_ROWMAJOR == 2 || (DQRM_COAL_ROWMAJOR == 1 && a.D >= 32);  // stage layout
     if (la) {
         if (!coalesce_apply_resident(a.T, stream)) return hipErrorInvalidValue;  // not all resident at once
-        static const uint32_t spin = [] {  // DQRM_STALL_SPIN: rendezvous polls before a stall (tests)
-            const char* e = getenv("DQRM_STALL_SPIN");
-            return e ? (uint32_t)strtoul(e, nullptr, 10) : (1u << 20);
-        }();
         LocalApplyArgs l2 = *la;
-        l2.spin_limit = spin;
+        l2.spin_limit = env_stall_spin();
         const bool fwd = l2.fwd_idx != nullptr;
 #define P1_LAUNCH(AP, FW, W_)                                                                                     \
     do {                                                                                                          \

@@ -23,13 +23,67 @@ DQRM_HIDDEN __attribute__((format(printf, 2, 3))) int set_error(int code, const 
             return dqrm_internal::set_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
     } while (0)
 
-// Which once-written streams the kernels store write-through (16-B sc1 stores, dqrm_device.h
-// st4_out): bits WT_Y / WT_HAND. DQRM_WT_STORES=0|y|hand|all in the environment (A/B), read
-// once per process (dqrm_kernels.hip); the launchers pass it on as a kernel argument or pick
-// the kernel instance by it. dim: the tables' row length -- y rows under 128 B (D < 32) stay
-// plain whatever the switch says: a 64-B row is half an L2 line, and written through it lost
-// (Kaggle, D = 16: 27.36 vs 27.03 us per step).
+// ---- The environment switches: one accessor each, all defined in one block of dqrm_kernels.hip,
+// the only place of libdqrm that reads a DQRM_* variable ("Environment
+// switches", lists them for users). Every switch is an A/B or test handle on a choice DESIGN.md 8
+// measured; unset, each leaves the measured default. Unless said otherwise a switch is read once
+// per process, on its first use.
+
+// DQRM_WT_STORES=0|y|hand|all (default y): which once-written streams the kernels store
+// write-through (16-B sc1 stores, dqrm_device.h st4_out): none / the forwards' y (WT_Y) / the
+// N > 1 hand-over buffers (WT_HAND) / both. The launchers pass the bits on as a kernel argument
+// or pick the kernel instance by them. dim: the tables' row length -- y rows under 128 B (D < 32)
+// stay plain whatever the switch says: a 64-B row is half an L2 line, and written through it lost
+// (Kaggle, D = 16: 27.36 vs 27.03 us per step; DESIGN.md 8, "write-through stores").
 DQRM_HIDDEN uint32_t wt_stores(int dim);
+// DQRM_APPLY=flat|slot|ranges|merge (default: DQRM_APPLY_AUTO): the apply kernel of
+// dqrm_apply_sparse_update*, as a DQRM_APPLY_* kind. Seeds the process's choice on its first
+// use; dqrm_set_apply_kernel overrides it. (tools/bench_apply_ranks.py)
+DQRM_HIDDEN int env_apply();
+// DQRM_FINALIZE=launch|inline (default 0 = per kernel: the flat apply kernels finalize the |W|
+// hierarchy with a k_table_finalize launch, the slot kernels inside their launch): 1 / 2 force
+// the launch / the in-launch hand-off for every kernel.
+DQRM_HIDDEN int env_finalize();
+// DQRM_FIN_FLAGGED=0 (default on): the finalize behind a flat apply visits only the tables the
+// kernel flagged; 0 finalizes every table.
+DQRM_HIDDEN bool env_fin_flagged();
+// DQRM_FUSED_FWD=0 (default on): the next batch's forward rides in the update's launch
+// (k_sgd_small, the one-launch local step, the merge apply); 0 keeps it a launch of its own.
+DQRM_HIDDEN bool env_fused_fwd();
+// DQRM_FIN_FWD=0 (default on): the flat apply's finalize and the next forward share one launch
+// (k_finalize_fwd); 0 restores the two launches.
+DQRM_HIDDEN bool env_fin_fwd();
+// DQRM_LOCAL_FUSED=0 (default on): dqrm_emb_bwd_apply_local runs coalesce + update as one launch
+// where it can; 0 always takes the two calls.
+DQRM_HIDDEN bool env_local_fused();
+// DQRM_QPACK=legacy (default off): dqrm_grad_quant_pack* runs the one-workgroup-per-slot
+// k_quant_pack instead of dqrm_exchange.hip's kernel.
+DQRM_HIDDEN bool env_qpack_legacy();
+// DQRM_MERGE_KEYS=<n> (default 256; n <= 0 counts as unset): payload entries of all ranks per
+// k_merge_pos workgroup, from which the merge apply sizes its chunks.
+DQRM_HIDDEN int64_t env_merge_keys();
+// DQRM_MERGE_DIAG=<n> (default 0): timing experiments only -- phases of k_merge_pos skipped, the
+// results are then wrong.
+DQRM_HIDDEN int env_merge_diag();
+// DQRM_FLAT_DUAL=0|1|4 (default -1 = unset: by size, cap_total >= 512 * T): entries per lane
+// group of the flat apply at 1 < N ranks: 0 one, 1 two (k_apply_flat2<.., 2>), 4 four. Read on
+// EVERY call: tests switch it inside one process.
+DQRM_HIDDEN int env_flat_dual();
+// DQRM_GATE_SPIN=<polls> (default 2^20): polls of a table's gate before a fused forward's
+// workgroup flags DQRM_ERRF_STALL (k_finalize_fwd, the merge apply's forward).
+DQRM_HIDDEN uint32_t env_gate_spin();
+// DQRM_STALL_SPIN=<polls> (default 2^20): rendezvous polls of the one-launch local step before a
+// workgroup gives up and flags DQRM_ERRF_STALL (tests shorten it).
+DQRM_HIDDEN uint32_t env_stall_spin();
+// DQRM_SUBSLOTS=0 (default on): the one-launch local step halves the largest tables' slots
+// between its spare workgroup groups; 0 leaves them idle.
+DQRM_HIDDEN bool env_subslots();
+// DQRM_SUBSLOT_ORDER=small (default: largest first): the smallest eligible tables get the
+// sub-slots first.
+DQRM_HIDDEN bool env_subslot_small_first();
+// DQRM_TABLE_GROUPS=critical (default off): the one-launch local step deals the tables expected
+// to end last onto the XCDs first.
+DQRM_HIDDEN bool env_table_groups_critical();
 
 // dqrm_linear.hip: what every dqrm_linear_* export rejects in a layer (quantized: the integer
 // buffers and bit widths as well) and in an activation code. Texts are "<who>: <fault>".

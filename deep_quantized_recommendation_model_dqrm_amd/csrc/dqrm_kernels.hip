@@ -69,20 +69,97 @@ int dqrm_internal::set_error(int code, const char* fmt, ...) {
     return code;
 }
 
-// DQRM_WT_STORES=0|y|hand|all (A/B): none / the forwards' y / the N > 1 hand-over buffers / both.
+// ------------------------------------------------------------------------------------
+// The environment switches (host): every DQRM_* variable libdqrm reads is read here and nowhere
+// else; dqrm_internal.h documents each accessor (values, default, what it selects), and
+// INTEGRATION.md lists them all. Read once per process, on first use, unless said otherwise.
+// ------------------------------------------------------------------------------------
+static bool env_is(const char* e, const char* value) { return e && !strcmp(e, value); }
+static uint32_t env_u32(const char* e, uint32_t dflt) { return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt; }
+
 // Unset or anything else: the default, y ("write-through stores of once-written
 // outputs": the hand-over buffers gained on the forced-collectives line only and moved no
 // WRITE_SIZE, the wide tables' W rows did not gain and are not in the code).
 uint32_t dqrm_internal::wt_stores(int dim) {
     static const uint32_t v = [] {
         const char* e = getenv("DQRM_WT_STORES");
-        if (e && !strcmp(e, "0")) return 0u;
-        if (e && !strcmp(e, "y")) return WT_Y;
-        if (e && !strcmp(e, "hand")) return WT_HAND;
-        if (e && !strcmp(e, "all")) return WT_Y | WT_HAND;
+        if (env_is(e, "0")) return 0u;
+        if (env_is(e, "hand")) return WT_HAND;
+        if (env_is(e, "all")) return WT_Y | WT_HAND;
         return WT_Y;
     }();
     return dim * (int)sizeof(float) >= 128 ? v : v & ~WT_Y;  // y rows of whole L2 lines only
+}
+int dqrm_internal::env_apply() {  // not cached here: apply_kernel_kind() holds the value
+    const char* e = getenv("DQRM_APPLY");
+    return env_is(e, "flat") ? DQRM_APPLY_FLAT : env_is(e, "slot") ? DQRM_APPLY_SLOT
+           : env_is(e, "ranges") ? DQRM_APPLY_RANGES : env_is(e, "merge") ? DQRM_APPLY_MERGE : DQRM_APPLY_AUTO;
+}
+int dqrm_internal::env_finalize() {
+    static const int v = [] {
+        const char* e = getenv("DQRM_FINALIZE");
+        return env_is(e, "launch") ? 1 : env_is(e, "inline") ? 2 : 0;
+    }();
+    return v;
+}
+bool dqrm_internal::env_fin_flagged() {
+    static const bool off = env_is(getenv("DQRM_FIN_FLAGGED"), "0");
+    return !off;
+}
+bool dqrm_internal::env_fused_fwd() {
+    static const bool off = env_is(getenv("DQRM_FUSED_FWD"), "0");
+    return !off;
+}
+bool dqrm_internal::env_fin_fwd() {
+    static const bool off = env_is(getenv("DQRM_FIN_FWD"), "0");
+    return !off;
+}
+bool dqrm_internal::env_local_fused() {
+    static const bool off = env_is(getenv("DQRM_LOCAL_FUSED"), "0");
+    return !off;
+}
+bool dqrm_internal::env_qpack_legacy() {
+    static const bool v = env_is(getenv("DQRM_QPACK"), "legacy");
+    return v;
+}
+int64_t dqrm_internal::env_merge_keys() {
+    static const int64_t v = [] {
+        const char* e = getenv("DQRM_MERGE_KEYS");
+        const long k = e ? atol(e) : 256;
+        return (int64_t)(k > 0 ? k : 256);
+    }();
+    return v;
+}
+int dqrm_internal::env_merge_diag() {
+    static const int v = [] {
+        const char* e = getenv("DQRM_MERGE_DIAG");
+        return e ? atoi(e) : 0;
+    }();
+    return v;
+}
+int dqrm_internal::env_flat_dual() {  // read on every call: tests switch it inside one process
+    const char* e = getenv("DQRM_FLAT_DUAL");
+    return e ? atoi(e) : -1;
+}
+uint32_t dqrm_internal::env_gate_spin() {
+    static const uint32_t v = env_u32(getenv("DQRM_GATE_SPIN"), 1u << 20);
+    return v;
+}
+uint32_t dqrm_internal::env_stall_spin() {
+    static const uint32_t v = env_u32(getenv("DQRM_STALL_SPIN"), 1u << 20);
+    return v;
+}
+bool dqrm_internal::env_subslots() {
+    static const bool off = env_is(getenv("DQRM_SUBSLOTS"), "0");
+    return !off;
+}
+bool dqrm_internal::env_subslot_small_first() {
+    static const bool v = env_is(getenv("DQRM_SUBSLOT_ORDER"), "small");
+    return v;
+}
+bool dqrm_internal::env_table_groups_critical() {
+    static const bool v = env_is(getenv("DQRM_TABLE_GROUPS"), "critical");
+    return v;
 }
 
 namespace {
@@ -2266,7 +2343,7 @@ DQRM_INLINE void find_rows(const int32_t* const* rs, const int* ns, const int32_
 // each lane group takes TWO entries of rank r's payload (e and e + G), whose searches in the other
 // ranks' slot runs, value loads and row loads share their round trips -- twice the entries in
 // flight per wave at nearly the same registers. Same arithmetic, ownership and |W| upkeep.
-// Taken when the tables average >= 512 entries (apply_update_ex); DQRM_FLAT_DUAL=0/1 forces it.
+// Taken when the tables average >= 512 entries (apply_plan); DQRM_FLAT_DUAL=0/1 forces it.
 template <int LPR, int E>
 __global__ void __launch_bounds__(FLAT_TPB) k_apply_flat2(ApplyArgs a) {
     constexpr int D = LPR * 4;
@@ -3972,52 +4049,6 @@ __global__ void __launch_bounds__(256) k_rowwise_bag(const uint8_t* __restrict__
 }
 
 // ------------------------------------------------------------------------------------
-// host helpers
-// ------------------------------------------------------------------------------------
-int check_set(const dqrm_table_set* s) {
-    if (!s) return set_error(DQRM_E_INVALID, "dqrm: null table set");
-    if (s->num_tables <= 0 || s->num_tables > MAX_TABLES)
-        return set_error(DQRM_E_INVALID, "dqrm: num_tables out of range (%d)", s->num_tables);
-    const int D = s->dim;
-    if (D < 4 || D > 256 || (D & 3) || ((D / 4) & (D / 4 - 1)))
-        return set_error(DQRM_E_INVALID, "dqrm: dim must be 4*2^k <= 256 (got %d)", D);
-    if (!s->W || !s->rowmax || !s->blkmax || !s->sblkmax || !s->tmax || !s->scale || !s->pscale ||
-        !s->meta || !s->err || !s->tflags || !s->sdirty || !s->bdirty || !s->sync)
-        return set_error(DQRM_E_INVALID, "dqrm: null state pointer");
-    if (((uintptr_t)s->W) & 15)
-        return set_error(DQRM_E_INVALID, "dqrm: W must be 16-byte aligned");
-    return DQRM_OK;
-}
-
-// tracked: the preceding kernel raised tmax for every grown row (the flat apply kernels)
-// flagged: after the flat apply kernels (k_apply_flat / k_apply_local), which mark the tables
-// they flagged (FLAG_WORD) and keep narrow tables' maxima themselves
-static bool fin_flagged_skip() {  // DQRM_FIN_FLAGGED=0: finalize every table (A/B)
-    static const bool no_skip = [] {
-        const char* e = getenv("DQRM_FIN_FLAGGED");
-        return e && !strcmp(e, "0");
-    }();
-    return !no_skip;
-}
-
-int launch_finalize(const dqrm_table_set* set, hipStream_t st, bool tracked = false, bool flagged = false) {
-    static_assert(BLK <= 1024, "finalize: one thread per row of a narrow table");
-    if (!fin_flagged_skip()) flagged = false;
-    hipLaunchKernelGGL(k_table_finalize, dim3(set->num_tables), dim3(1024), 0, st, set->W, set->rowmax,
-                       set->blkmax, set->sblkmax, set->sdirty, set->bdirty, set->tmax, set->meta, set->num_tables,
-                       set->dim, tracked ? 1 : 0, set->sync, flagged ? 1 : 0);
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-int grid_for(int64_t work_items, int threads, int max_blocks = 2048) {
-    int64_t b = (work_items + threads - 1) / threads;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return (int)b;
-}
-
-// ------------------------------------------------------------------------------------
 // Rows rewritten outside libdqrm (torch.optim.SGD stepping on the grad_mode="sparse" COO):
 // one lane group per listed slab row recomputes its rowmax (and, repack, its INT4 row with
 // the frozen pscale) and flags its block and superblock; the untracked finalize then
@@ -4173,6 +4204,108 @@ __global__ void __launch_bounds__(256) k_lookup_grad(LgArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------
+// host helpers
+// ------------------------------------------------------------------------------------
+int check_set(const dqrm_table_set* s) {
+    if (!s) return set_error(DQRM_E_INVALID, "dqrm: null table set");
+    if (s->num_tables <= 0 || s->num_tables > MAX_TABLES)
+        return set_error(DQRM_E_INVALID, "dqrm: num_tables out of range (%d)", s->num_tables);
+    const int D = s->dim;
+    if (D < 4 || D > 256 || (D & 3) || ((D / 4) & (D / 4 - 1)))
+        return set_error(DQRM_E_INVALID, "dqrm: dim must be 4*2^k <= 256 (got %d)", D);
+    if (!s->W || !s->rowmax || !s->blkmax || !s->sblkmax || !s->tmax || !s->scale || !s->pscale ||
+        !s->meta || !s->err || !s->tflags || !s->sdirty || !s->bdirty || !s->sync)
+        return set_error(DQRM_E_INVALID, "dqrm: null state pointer");
+    if (((uintptr_t)s->W) & 15)
+        return set_error(DQRM_E_INVALID, "dqrm: W must be 16-byte aligned");
+    return DQRM_OK;
+}
+
+// The checks several exports share; `who` is the export name the text reports.
+int check_batch(const dqrm_batch* batch, const char* who) {
+    if (!batch || !batch->idx || !batch->off || !batch->idx_base)
+        return set_error(DQRM_E_INVALID, "%s: null batch pointer", who);
+    if (batch->num_bags > 0xFFFFFFFFll)
+        return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 bags", who);
+    return DQRM_OK;
+}
+
+int check_dy(const float* dy, int64_t dy_stride_t, int64_t dy_stride_b, const char* who) {
+    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
+        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", who);
+    return DQRM_OK;
+}
+
+int check_repack(const dqrm_table_set* set, int repack_bits, const char* who) {
+    if (repack_bits && (repack_bits != 4 || !set->packed))
+        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", who, repack_bits);
+    return DQRM_OK;
+}
+
+// the coalesced-gradient slot workspace; rest_ok: what else the caller needs of it (s_avg, a total)
+int check_slot_ws(const int64_t* ws_cap_base, const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
+                  const float* ws_absmax, const char* who, bool rest_ok = true) {
+    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || !rest_ok || (((uintptr_t)ws_vals) & 15))
+        return set_error(DQRM_E_INVALID, "%s: null/unaligned workspace", who);
+    return DQRM_OK;
+}
+
+// the forward's argument checks (every entry point that runs a forward)
+int check_fwd(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags, const float* out,
+              int64_t out_stride_t, int64_t out_stride_b, const char* who) {
+    int rc = check_set(set);
+    if (rc) return rc;
+    if (!batch || !batch->idx || !batch->off || !batch->idx_base || !out)
+        return set_error(DQRM_E_INVALID, "%s: null batch/out pointer", who);
+    if (!(flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
+        return set_error(DQRM_E_INVALID, "%s: embedding_bit %d unsupported", who, bits);
+    if ((flags & DQRM_FWD_USE_PACKED) && (!set->packed || bits != 4))
+        return set_error(DQRM_E_INVALID, "%s: packed path needs packed rows and bits == 4", who);
+    if ((((uintptr_t)out) & 15) || (out_stride_t & 3) || (out_stride_b & 3))
+        return set_error(DQRM_E_INVALID, "%s: out must be 16-B aligned with strides %% 4 == 0", who);
+    return DQRM_OK;
+}
+
+// what dqrm_apply_sparse_update, _strided and _fwd reject in the apply's arguments (all three
+// report under the first one's name)
+int check_apply(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total, const void* payloads,
+                size_t payload_bytes, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg, int mode,
+                int repack_bits) {
+    int rc = check_set(set);
+    if (rc) return rc;
+    if (num_ranks <= 0 || num_ranks > DQRM_MAX_RANKS || !payloads || !cap_base)
+        return set_error(DQRM_E_INVALID, "%s: bad ranks/payloads (%d)", "dqrm_apply_sparse_update", num_ranks);
+    if (mode == DQRM_UPD_FP32 ? grad_bits != 32 : (grad_bits < 2 || grad_bits > 16 || !s_avg))
+        return set_error(DQRM_E_INVALID, "%s: mode/grad_bits mismatch (%d)", "dqrm_apply_sparse_update", grad_bits);
+    if (payload_bytes != dqrm_payload_bytes(set->num_tables, cap_total, set->dim, grad_bits))
+        return set_error(DQRM_E_INVALID, "%s: payload_bytes mismatch", "dqrm_apply_sparse_update");
+    if (rank_pitch < payload_bytes || (rank_pitch & 15) || (((uintptr_t)payloads) & 15))
+        return set_error(DQRM_E_INVALID, "%s: rank pitch %zu / payload alignment", "dqrm_apply_sparse_update",
+                         rank_pitch);
+    return check_repack(set, repack_bits, "dqrm_apply_sparse_update");
+}
+
+// tracked: the preceding kernel raised tmax for every grown row (the flat apply kernels)
+// flagged: after the flat apply kernels (k_apply_flat / k_apply_local), which mark the tables
+// they flagged (FLAG_WORD) and keep narrow tables' maxima themselves
+int launch_finalize(const dqrm_table_set* set, hipStream_t st, bool tracked = false, bool flagged = false) {
+    static_assert(BLK <= 1024, "finalize: one thread per row of a narrow table");
+    if (!dqrm_internal::env_fin_flagged()) flagged = false;
+    hipLaunchKernelGGL(k_table_finalize, dim3(set->num_tables), dim3(1024), 0, st, set->W, set->rowmax,
+                       set->blkmax, set->sblkmax, set->sdirty, set->bdirty, set->tmax, set->meta, set->num_tables,
+                       set->dim, tracked ? 1 : 0, set->sync, flagged ? 1 : 0);
+    LAUNCH_CHECK();
+    return DQRM_OK;
+}
+
+int grid_for(int64_t work_items, int threads, int max_blocks = 2048) {
+    int64_t b = (work_items + threads - 1) / threads;
+    if (b < 1) b = 1;
+    if (b > max_blocks) b = max_blocks;
+    return (int)b;
+}
+
 #define DISPATCH_LPR(D, ...)                                  \
     switch ((D) / 4) {                                        \
         case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;  \
@@ -4185,42 +4318,50 @@ __global__ void __launch_bounds__(256) k_lookup_grad(LgArgs a) {
         default: return set_error(DQRM_E_INVALID, "dqrm: unsupported dim %d", (int)(D)); \
     }
 
+constexpr int LDS_PER_CU = 160 * 1024;  // gfx950: static + dynamic LDS of one workgroup
+
+// What the launch path remembers of a kernel's LDS, per kernel address (several kernels share one
+// function-pointer type): the dynamic bytes already allowed and the static bytes. Both cost a
+// runtime call, taken once per kernel and not on every launch. A full cache only stops caching.
+struct KernelLds {
+    const void* f;
+    size_t allowed;      // hipFuncAttributeMaxDynamicSharedMemorySize as set here (0: the default)
+    int64_t static_lds;  // hipFuncGetAttributes' sharedSizeBytes, -1 not asked yet
+};
+std::mutex g_kernel_lds_mu;  // launches may come from several host threads
+KernelLds* kernel_lds(const void* f) {  // under g_kernel_lds_mu; nullptr: cache full
+    static KernelLds seen[64];
+    static int nseen = 0;
+    for (int i = 0; i < nseen; ++i)
+        if (seen[i].f == f) return &seen[i];
+    if (nseen == 64) return nullptr;
+    seen[nseen] = KernelLds{f, 0, -1};
+    return &seen[nseen++];
+}
+
 // allow the per-table kernels more than the default 64 KiB of dynamic LDS (gfx950: 160 KiB/CU)
 template <typename K>
 int allow_lds(K kernel, size_t bytes) {
-    // once per kernel instantiation and size (the attribute is per-function, process-wide;
-    // re-setting it on every call costs host time on the launch path)
-    // (keyed by the kernel's address: several kernels share one function-pointer type)
     if (bytes <= 65536) return DQRM_OK;
-    static std::mutex mu;  // launches may come from several host threads
-    std::lock_guard<std::mutex> lock(mu);
-    static const void* seen[64];
-    static size_t seen_bytes[64];
-    static int nseen = 0;
     const void* f = reinterpret_cast<const void*>(kernel);
-    for (int i = 0; i < nseen; ++i)
-        if (seen[i] == f && seen_bytes[i] >= bytes) return DQRM_OK;
+    std::lock_guard<std::mutex> lock(g_kernel_lds_mu);
+    KernelLds* k = kernel_lds(f);
+    if (k && k->allowed >= bytes) return DQRM_OK;
     DQRM_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    if (nseen < 64) { seen[nseen] = f; seen_bytes[nseen] = bytes; ++nseen; }
+    if (k) k->allowed = bytes;
     return DQRM_OK;
 }
 
-constexpr int LDS_PER_CU = 160 * 1024;  // gfx950: static + dynamic LDS of one workgroup
-
-// a kernel's static LDS bytes (hipFuncGetAttributes, cached per kernel address)
+// a kernel's static LDS bytes
 template <typename K>
 size_t static_lds_bytes(K kernel) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    static const void* seen[64];
-    static size_t seen_bytes[64];
-    static int nseen = 0;
     const void* f = reinterpret_cast<const void*>(kernel);
-    for (int i = 0; i < nseen; ++i)
-        if (seen[i] == f) return seen_bytes[i];
+    std::lock_guard<std::mutex> lock(g_kernel_lds_mu);
+    KernelLds* k = kernel_lds(f);
+    if (k && k->static_lds >= 0) return (size_t)k->static_lds;
     hipFuncAttributes at{};
     if (hipFuncGetAttributes(&at, f) != hipSuccess) return (size_t)LDS_PER_CU;  // unknown: treat as full
-    if (nseen < 64) { seen[nseen] = f; seen_bytes[nseen] = at.sharedSizeBytes; ++nseen; }
+    if (k) k->static_lds = (int64_t)at.sharedSizeBytes;
     return at.sharedSizeBytes;
 }
 
@@ -4233,12 +4374,8 @@ std::atomic<int> g_apply_kernel{-1};
 int apply_kernel_kind() {
     int k = g_apply_kernel.load();
     if (k < 0) {
-        const char* e = getenv("DQRM_APPLY");
-        k = (e && !strcmp(e, "flat")) ? DQRM_APPLY_FLAT : (e && !strcmp(e, "slot")) ? DQRM_APPLY_SLOT
-            : (e && !strcmp(e, "ranges")) ? DQRM_APPLY_RANGES : (e && !strcmp(e, "merge")) ? DQRM_APPLY_MERGE
-            : DQRM_APPLY_AUTO;
         int expect = -1;
-        g_apply_kernel.compare_exchange_strong(expect, k);
+        g_apply_kernel.compare_exchange_strong(expect, dqrm_internal::env_apply());
         k = g_apply_kernel.load();
     }
     return k;
@@ -4250,15 +4387,32 @@ int apply_kernel_kind() {
 // the in-launch hand-off (whose code and arrival protocol cost them occupancy and a tail
 // round trip per workgroup); the slot kernels (one workgroup per table slot) finalize in
 // the launch. DQRM_FINALIZE=launch / inline forces one scheme for every kernel (A/B).
-int finalize_mode() {  // 0 auto, 1 launch, 2 inline
-    static const int v = [] {
-        const char* e = getenv("DQRM_FINALIZE");
-        return (e && !strcmp(e, "launch")) ? 1 : (e && !strcmp(e, "inline")) ? 2 : 0;
-    }();
-    return v;
+using dqrm_internal::env_finalize;  // 0 per kernel, 1 launch, 2 inline
+int finalize_launch() { return env_finalize() == 1 ? 1 : 0; }          // slot kernels
+int finalize_launch_flat() { return env_finalize() == 2 ? 0 : 1; }     // flat apply kernels
+
+// The forward of the NEXT batch that an update call also runs (next == nullptr: none): the
+// arguments of dqrm_emb_fwd, carried as one value through the SGD call, the local step and the apply
+struct FusedFwd {
+    const dqrm_batch* next;
+    int bits;
+    uint32_t flags;
+    float* out;
+    int64_t ost_t, ost_b;
+};
+
+// the forward's kernel arguments from arguments check_fwd passed
+FwdArgs fwd_args(const dqrm_table_set* set, const FusedFwd& f) {
+    FwdArgs a;
+    a.W = set->W; a.packed = set->packed; a.tmax = set->tmax; a.scale = set->scale;
+    a.meta = set->meta; a.err = set->err;
+    a.idx = f.next->idx; a.off = f.next->off; a.idx_base = f.next->idx_base;
+    a.pool1 = (f.next->flags & DQRM_BATCH_POOLING_ONE) != 0;
+    a.out = f.out; a.B = f.next->num_bags; a.ost_t = f.ost_t; a.ost_b = f.ost_b;
+    a.T = set->num_tables; a.bits = f.bits; a.flags = f.flags;
+    a.wt = dqrm_internal::wt_stores(set->dim);
+    return a;
 }
-int finalize_launch() { return finalize_mode() == 1 ? 1 : 0; }          // slot kernels
-int finalize_launch_flat() { return finalize_mode() == 2 ? 0 : 1; }     // flat apply kernels
 
 // one backward call (K4a + K4b [+ finalize]) on the caller's workspace
 struct BwdCall {
@@ -4278,51 +4432,251 @@ struct BwdCall {
     void* ws;
     size_t ws_bytes;
     float div = 1.0f;
-    // MODE 0: the next batch's forward (dqrm_emb_bwd_sgd_fwd); taken inside k_sgd_small when it
-    // runs, else a dqrm_emb_fwd launch after the update
-    const dqrm_batch* next = nullptr;
-    int fwd_bits = 4;
-    uint32_t fwd_flags = 0;
-    float* fwd_out = nullptr;
-    int64_t fwd_ost_t = 0, fwd_ost_b = 0;
+    // MODE 0: the next batch's forward (dqrm_emb_bwd_sgd_fwd), where the SgdPlan puts it
+    FusedFwd fwd{};
 };
 
 int64_t bwd_lookup_cap(const dqrm_batch* batch) { return batch->max_lookups > 0 ? batch->max_lookups : 1; }
 
-bool fused_sgd_fwd_on() {  // DQRM_FUSED_FWD=0: the next batch's forward as its own launch (A/B)
-    static const bool off = [] {
-        const char* e = getenv("DQRM_FUSED_FWD");
-        return e && !strcmp(e, "0");
-    }();
-    return !off;
+// ------------------------------------------------------------------------------------
+// Plans: which launches an entry point issues for its arguments. A plan is a small value from a
+// function that launches nothing and sets no error; the launcher executes it and the queries
+// (dqrm_*_is_one_launch, dqrm_apply_fwd_form, emb_bwd_sgd_launches) read it, so what a query
+// says is what the launcher does.
+// ------------------------------------------------------------------------------------
+
+// The INT4 packed gather takes a forward with these flags (k_emb_fwd_packed; else k_emb_fwd).
+bool fwd_packed_path(int dim, uint32_t flags) {
+    return (flags & DQRM_FWD_USE_PACKED) && !(flags & DQRM_FWD_FULL_PRECISION) && dim >= 8;
 }
 
-// Whether k_sgd_small takes an SGD call (MODE 0) of this batch, and whether the next batch's
-// forward then runs inside it: returns 0 (k_bwd_fused), 1 (k_sgd_small, forward apart or none),
-// 2 (k_sgd_small with the forward in the launch)
-int sgd_small_plan(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, uint32_t fwd_flags,
-                   size_t* dyn_out) {
+// The next batch's forward can ride in an update's launch: a Criteo-form batch on the exact FP32
+// rows (a forward asked for with DQRM_FWD_USE_PACKED stays a launch of its own), DQRM_FUSED_FWD
+// not 0. Each update adds its own term on num_bags.
+bool fwd_can_ride(const dqrm_batch* next, uint32_t flags) {
+    return dqrm_internal::env_fused_fwd() && next && (next->flags & DQRM_BATCH_POOLING_ONE) &&
+           next->max_lookups >= next->num_bags && !(flags & DQRM_FWD_USE_PACKED);
+}
+
+// The Criteo-form coalesce kernel (k_coalesce_p1) takes this batch; else the general kernel.
+bool coalesce_takes_pool1(const dqrm_table_set* set, const dqrm_batch* batch) {
+    return g_coalesce_kernel.load() == DQRM_COALESCE_AUTO && (batch->flags & DQRM_BATCH_POOLING_ONE) &&
+           batch->num_bags <= dqrm_internal::kCoalesceMaxB && batch->max_lookups >= batch->num_bags &&
+           set->total_rows <= 0xffffffffll;
+}
+
+// dqrm_emb_bwd_sgd (next == nullptr) / dqrm_emb_bwd_sgd_fwd on a checked set and batches
+struct SgdPlan {
+    bool small;       // k_sgd_small (one workgroup per table, finalized in the launch), else k_bwd_fused
+    bool fwd_inside;  // small, and the next batch's forward runs in that launch
+    size_t dyn;       // small: k_sgd_small's dynamic LDS bytes
+    int launches;     // the kernel + k_bwd_fused's finalize launch if any + a forward launch if any
+};
+
+size_t sgd_small_static_lds(int D, bool fwd) {
+    switch (D / 4) {
+#define SG_CASE(L) \
+    case L: return fwd ? static_lds_bytes(k_sgd_small<L, true>) : static_lds_bytes(k_sgd_small<L, false>)
+        SG_CASE(1); SG_CASE(2); SG_CASE(4); SG_CASE(8); SG_CASE(16); SG_CASE(32); SG_CASE(64);
+#undef SG_CASE
+    }
+    return (size_t)LDS_PER_CU;  // no such kernel: does not fit
+}
+
+SgdPlan sgd_plan(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, uint32_t fwd_flags) {
+    SgdPlan p{};
     const int D = set->dim;
-    const int64_t Lc = bwd_lookup_cap(batch);
-    if (!(g_coalesce_kernel.load() == DQRM_COALESCE_AUTO && Lc <= sg_maxl(D / 4) &&
-          batch->num_bags * D <= SG_DY_FLOATS && set->total_rows <= 0x7fffffffll))
-        return 0;
-    // dy staging, then (Criteo form) the row hash; the kernel reads L = B lookups per table.
-    // It takes the batch only if that dynamic LDS plus its static LDS fit one CU (else
-    // k_bwd_fused, which has no per-batch LDS).
-    const bool p1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
-    const size_t dyn = (size_t)batch->num_bags * D * sizeof(float) + (p1 ? (size_t)sg_hash_bytes((int)batch->num_bags) : 0);
-    // the next batch's forward inside the launch: a Criteo-form batch of the same size on
-    // the exact FP32 rows (the packed INT4 path stays a launch of its own)
-    const bool fwd = next && (next->flags & DQRM_BATCH_POOLING_ONE) && next->num_bags == batch->num_bags &&
-                     next->max_lookups >= next->num_bags && !(fwd_flags & DQRM_FWD_USE_PACKED) && fused_sgd_fwd_on();
-    bool fits = false;
+    // the next batch's forward inside the launch: one of the same size
+    const bool fwd = fwd_can_ride(next, fwd_flags) && next->num_bags == batch->num_bags;
+    if (g_coalesce_kernel.load() == DQRM_COALESCE_AUTO && bwd_lookup_cap(batch) <= sg_maxl(D / 4) &&
+        batch->num_bags * D <= SG_DY_FLOATS && set->total_rows <= 0x7fffffffll) {
+        // dy staging, then (Criteo form) the row hash; the kernel reads L = B lookups per table.
+        // It takes the batch only if that dynamic LDS plus its static LDS fit one CU (else
+        // k_bwd_fused, which has no per-batch LDS).
+        const bool p1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
+        p.dyn = (size_t)batch->num_bags * D * sizeof(float) + (p1 ? (size_t)sg_hash_bytes((int)batch->num_bags) : 0);
+        p.small = p.dyn + sgd_small_static_lds(D, fwd) <= (size_t)LDS_PER_CU;
+    }
+    p.fwd_inside = p.small && fwd;
+    const int fwd_launch = next && next->num_bags > 0 ? 1 : 0;
+    if (batch->num_bags <= 0) p.launches = fwd_launch;  // nothing to update: the exports run the forward alone
+    else p.launches = 1 + (p.small ? 0 : finalize_launch()) + (p.fwd_inside ? 0 : fwd_launch);
+    return p;
+}
+
+// recover the per-rank batch B from cap_total = sum_t min(B, n_t) (host row counts), -1 without them
+int64_t recover_batch(const dqrm_table_set* set, int64_t cap_total) {
+    const int64_t* nr = set->num_rows_host;
+    if (!nr) return -1;
+    int64_t lo = 0, hi = 0;
+    for (int t = 0; t < set->num_tables; ++t) hi = nr[t] > hi ? nr[t] : hi;
+    while (lo < hi) {  // smallest B with sum_t min(B, n_t) >= cap_total
+        const int64_t mid = (lo + hi) / 2;
+        int64_t c = 0;
+        for (int t = 0; t < set->num_tables; ++t) c += nr[t] < mid ? nr[t] : mid;
+        if (c < cap_total) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// k_apply_pos: entry chunks per (table, rank) -- one pass of 4 entries per lane group covers the
+// largest table's capacity min(B, n_t) -- at most 32768 workgroups
+int merge_apply_gx(const dqrm_table_set* set, int64_t cap_total, int num_ranks, int D) {
+    const int64_t per = (256 / (D / 4)) * 4;  // entries per workgroup: (lane groups) x AP_INFL
+    const int64_t B = recover_batch(set, cap_total);
+    const int64_t cmax = B >= 0 ? B : cap_total;
+    int64_t gx = (cmax + per - 1) / per;
+    const int64_t lim = (32768 + (int64_t)set->num_tables * num_ranks - 1) / ((int64_t)set->num_tables * num_ranks);
+    gx = gx > lim ? lim : gx;
+    return (int)(gx < 1 ? 1 : gx);
+}
+
+// Chunks per row-range slot of each table for k_apply_merge: about DQRM_MERGE_KEYS (default 256)
+// payload entries of all ranks per workgroup, from the table's payload capacity min(B, n_t)
+// (B recovered from cap_total = sum_t min(B, n_t) and the host row counts; without those, an
+// even split), at most the slot's blocks (chunks are block-aligned) and at most 64.
+void merge_chunks(const dqrm_table_set* set, int64_t cap_total, int N, int* kt, int* kbase) {
+    const int64_t target = dqrm_internal::env_merge_keys();
+    const int T = set->num_tables;
+    const int64_t* nr = set->num_rows_host;
+    const int64_t B = recover_batch(set, cap_total);
+    kbase[0] = 0;
+    for (int t = 0; t < T; ++t) {
+        const int64_t cap_t = B >= 0 ? (nr[t] < B ? nr[t] : B) : (cap_total + T - 1) / T;
+        int64_t K = ((int64_t)N * cap_t + SPLIT * target - 1) / (SPLIT * target);
+        if (nr) {
+            const int64_t blocks_per_slot = ((nr[t] + BLK - 1) / BLK + SPLIT - 1) / SPLIT;
+            K = K < blocks_per_slot ? K : blocks_per_slot;
+        }
+        K = K < 1 ? 1 : (K > 64 ? 64 : K);
+        kt[t] = (int)K;
+        kbase[t + 1] = kbase[t] + SPLIT * (int)K;
+    }
+}
+
+// dqrm_emb_bwd_apply_local (next == nullptr) / dqrm_emb_bwd_apply_fwd_local on a checked set and
+// batches: one launch for Criteo-form batches whose grid can be resident at once (device CUs,
+// occupancy, the stream's CU mask), the two calls otherwise
+struct LocalPlan {
+    bool one_launch;  // coalesce + update in one launch (k_coalesce_p1), else dqrm_emb_bwd_coalesce + dqrm_apply_local
+    bool fwd_inside;  // one_launch, and the next batch's forward (one of the same size) runs in that launch
+};
+
+LocalPlan local_plan(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, uint32_t fwd_flags,
+                     void* stream) {
+    LocalPlan p{};
+    p.one_launch = dqrm_internal::env_local_fused() && coalesce_takes_pool1(set, batch) &&
+                   set->num_tables <= dqrm_internal::kCoalesceApplyMaxT &&
+                   dqrm_internal::coalesce_apply_resident(set->num_tables, (hipStream_t)stream);
+    p.fwd_inside = p.one_launch && fwd_can_ride(next, fwd_flags) && next->num_bags == batch->num_bags;
+    return p;
+}
+
+// dqrm_apply_sparse_update / _strided / _fwd on a checked set (and next batch, nullable)
+enum class ApplyKernel {
+    Merge,   // dqrm_apply_merge.hip: the ranks' rows merged in LDS, finalized in the launch
+    Ranges,  // dqrm_apply.hip: row ranges owned per workgroup, finalized in the launch
+    Slot,    // k_table_apply: one workgroup per table slot
+    Flat,    // k_apply_flat: one entry per lane group
+    Flat2,   // k_apply_flat2<.., 2>: two entries per lane group
+    Flat4,   // k_apply_flat2<.., 4>: four (two where a row has under 4 lanes: its LDS needs LPR >= 4)
+};
+enum class ApplyFin {  // where the |W| hierarchy is finalized
+    Inside,   // in the kernel's launch
+    Launch,   // a k_table_finalize launch behind it
+    WithFwd,  // a k_finalize_fwd launch behind it, which runs the next batch's forward as well
+};
+struct ApplyPlan {
+    ApplyKernel kernel;
+    ApplyFin fin;
+    int form;  // with a next batch: DQRM_APPLY_FWD_{SEPARATE, ONE_LAUNCH, FIN_FWD} (include/dqrm.h)
+};
+
+ApplyPlan apply_plan(const dqrm_table_set* set, int num_ranks, int64_t cap_total, size_t ws_bytes,
+                     const dqrm_batch* next, uint32_t fwd_flags) {
+    ApplyPlan p{ApplyKernel::Flat, ApplyFin::Inside, DQRM_APPLY_FWD_SEPARATE};
+    const int kind = apply_kernel_kind();
+    // The merge kernels only when asked for (DQRM_APPLY=merge / dqrm_set_apply_kernel) and the
+    // positions workspace is given (N = 1 needs none); else the flat kernel. Not AUTO: measured
+    // on the TB shape (profiles/r6_apply_ranks_*.txt) merge is not faster than the flat kernel +
+    // finalize launch at N = 1..8 (2048 per rank: 20.6 / 53.4 / 75.8 / 143 us vs 15.4 / 39.4 /
+    // 68.0 / 138.8 us).
+    if (kind == DQRM_APPLY_MERGE && num_ranks <= dqrm_internal::kMergeMaxRanks &&
+        set->num_tables <= dqrm_internal::kMergeMaxTables &&
+        ws_bytes >= dqrm_internal::apply_workspace_bytes(num_ranks, cap_total)) {
+        p.kernel = ApplyKernel::Merge;
+        // the forward in the grid's last workgroups, behind each table's gate
+        if (fwd_can_ride(next, fwd_flags) && next->num_bags > 0) p.form = DQRM_APPLY_FWD_ONE_LAUNCH;
+        return p;
+    }
+    if (kind == DQRM_APPLY_RANGES) {
+        p.kernel = ApplyKernel::Ranges;
+        return p;
+    }
+    // AUTO: flat while each lane of a row's group searches at most one other rank
+    // (num_ranks < D/4), slot beyond (tools/bench_apply_ranks.py, DESIGN.md section 8)
+    if (kind == DQRM_APPLY_SLOT || (kind == DQRM_APPLY_AUTO && num_ranks > 1 && num_ranks >= set->dim / 4)) {
+        p.kernel = ApplyKernel::Slot;
+        p.fin = finalize_launch() ? ApplyFin::Launch : ApplyFin::Inside;
+        return p;
+    }
+    if (!finalize_launch_flat()) return p;  // k_apply_flat finalizing in its launch
+    p.fin = ApplyFin::Launch;
+    // two entries per lane group when the tables hold enough entries to keep the chip busy
+    // at half the workgroups (same box, TB: 2048 per rank 129 vs 142 us at N = 8, 44 vs 48 at
+    // N = 2; 256 per rank slower: 20 vs 14 us at N = 2); DQRM_FLAT_DUAL=0/1 forces it
+    const int dual_env = dqrm_internal::env_flat_dual();
+    const bool dual = dual_env >= 0 ? dual_env != 0 : cap_total >= (int64_t)512 * set->num_tables;
+    if (dual && num_ranks > 1 && num_ranks <= FLAT_HDR_RANKS)
+        p.kernel = dual_env == 4 ? ApplyKernel::Flat4 : ApplyKernel::Flat2;
+    // its finalize launch together with the next forward (k_finalize_fwd): the exact FP32-row
+    // forward (the INT4 packed gather stays a launch of its own); DQRM_FIN_FWD=0 turns it off
+    if (dqrm_internal::env_fin_fwd() && next && next->num_bags > 0 && !fwd_packed_path(set->dim, fwd_flags)) {
+        p.fin = ApplyFin::WithFwd;
+        p.form = DQRM_APPLY_FWD_FIN_FWD;
+    }
+    return p;
+}
+
+// ------------------------------------------------------------------------------------
+// Launchers: each executes a plan
+// ------------------------------------------------------------------------------------
+int launch_fwd(const dqrm_table_set* set, const FusedFwd& f, hipStream_t st) {
+    if (f.next->num_bags <= 0) return DQRM_OK;
+    FwdArgs a = fwd_args(set, f);
+    const int D = set->dim;
+    if (fwd_packed_path(D, f.flags)) {
+        int64_t bx = (a.B + 255) / 256;
+        const int64_t cap = (16384 + a.T - 1) / a.T;
+        if (bx > cap) bx = cap;
+        const bool nt = (f.flags & DQRM_FWD_NT_STORE) != 0;
+        // y goes write-through only while the eight XCD L2s (32 MB) could hold all of it dirty at
+        // the kernel's end. A larger output is evicted as the kernel runs, the end's write-back
+        // is bounded by L2's size whatever the store, and the plain stream is what the 436 MB
+        // int4_gather line was tuned and measured with: kept. (The cut-off is reasoned; a
+        // write-through run of that line was not made.)
+        if ((int64_t)a.T * a.B * D * (int64_t)sizeof(float) > (32ll << 20)) a.wt &= ~WT_Y;
+        DISPATCH_LPR(D, {
+            if constexpr (LPR >= 2) {
+                if (nt)
+                    hipLaunchKernelGGL((k_emb_fwd_packed<LPR, true>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
+                else
+                    hipLaunchKernelGGL((k_emb_fwd_packed<LPR, false>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
+            }
+        });
+        LAUNCH_CHECK();
+        return DQRM_OK;
+    }
     DISPATCH_LPR(D, {
-        fits = dyn + (fwd ? static_lds_bytes(k_sgd_small<LPR, true>) : static_lds_bytes(k_sgd_small<LPR, false>)) <=
-               (size_t)LDS_PER_CU;
+        constexpr int UNR = 4;
+        constexpr int BAGS_PER_WG = (256 / LPR) * UNR;
+        int64_t bx = (a.B + BAGS_PER_WG - 1) / BAGS_PER_WG;
+        const int64_t cap = (8192 + a.T - 1) / a.T;  // ~8k workgroups in total, grid-stride beyond
+        if (bx > cap) bx = cap;
+        hipLaunchKernelGGL((k_emb_fwd<LPR, UNR>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
     });
-    if (dyn_out) *dyn_out = dyn;
-    return fits ? (fwd ? 2 : 1) : 0;
+    LAUNCH_CHECK();
+    return DQRM_OK;
 }
 
 template <int MODE>
@@ -4352,13 +4706,13 @@ int launch_bwd(const BwdCall& c, hipStream_t st, const char* who) {
     int rc = 0;
     // SGD of a small batch: one workgroup per table, no sort, no hand-off (k_sgd_small)
     if (MODE == 0) {
-        size_t dyn = 0;
-        const int plan = sgd_small_plan(set, c.batch, c.next, c.fwd_flags, &dyn);
-        const bool fwd = plan == 2;
-        if (plan > 0) {
+        const SgdPlan plan = sgd_plan(set, c.batch, c.fwd.next, c.fwd.flags);
+        const bool fwd = plan.fwd_inside;
+        const size_t dyn = plan.dyn;
+        if (plan.small) {
             if (fwd) {
-                fa.fwd_idx = c.next->idx; fa.fwd_out = c.fwd_out; fa.fwd_ost_t = c.fwd_ost_t; fa.fwd_ost_b = c.fwd_ost_b;
-                fa.fwd_scale = set->scale; fa.fwd_bits = c.fwd_bits; fa.fwd_flags = c.fwd_flags;
+                fa.fwd_idx = c.fwd.next->idx; fa.fwd_out = c.fwd.out; fa.fwd_ost_t = c.fwd.ost_t; fa.fwd_ost_b = c.fwd.ost_b;
+                fa.fwd_scale = set->scale; fa.fwd_bits = c.fwd.bits; fa.fwd_flags = c.fwd.flags;
                 fa.wt = dqrm_internal::wt_stores(D);
             }
             DISPATCH_LPR(D, {
@@ -4371,9 +4725,7 @@ int launch_bwd(const BwdCall& c, hipStream_t st, const char* who) {
                 }
             });
             LAUNCH_CHECK();
-            if (c.next && !fwd)
-                return dqrm_emb_fwd(set, c.next, c.fwd_bits, c.fwd_flags, c.fwd_out, c.fwd_ost_t, c.fwd_ost_b, st);
-            return DQRM_OK;
+            return c.fwd.next && !fwd ? launch_fwd(set, c.fwd, st) : DQRM_OK;
         }
     }
     DISPATCH_LPR(D, {
@@ -4382,12 +4734,191 @@ int launch_bwd(const BwdCall& c, hipStream_t st, const char* who) {
     });
     LAUNCH_CHECK();  // MODE 0 / 2: the |W| hierarchy is finalized inside the launch
     if (MODE != 1 && fa.fin_launch && (rc = launch_finalize(set, st, true))) return rc;
-    if (MODE == 0 && c.next)  // the next batch's forward as its own launch
-        return dqrm_emb_fwd(set, c.next, c.fwd_bits, c.fwd_flags, c.fwd_out, c.fwd_ost_t, c.fwd_ost_b, st);
+    if (MODE == 0 && c.fwd.next) return launch_fwd(set, c.fwd, st);  // the next batch's forward as its own launch
     return DQRM_OK;
 }
 
+// a flat apply's finalize and the next batch's forward in one launch (ApplyFin::WithFwd)
+int launch_finalize_fwd(const dqrm_table_set* set, FwdArgs fa, hipStream_t st) {
+    fa.sync = set->sync;
+    fa.spin = dqrm_internal::env_gate_spin();
+    FinArgs f{set->W, set->rowmax, set->blkmax, set->sblkmax, set->sdirty, set->bdirty, set->tmax, set->dim,
+              1, dqrm_internal::env_fin_flagged() ? 1 : 0};
+    DISPATCH_LPR(set->dim, {
+        constexpr int UNR = 4;
+        constexpr int BAGS_PER_WG = (FINFWD_TPB / LPR) * UNR;
+        int64_t bx = (fa.B + BAGS_PER_WG - 1) / BAGS_PER_WG;
+        const int64_t cap = (2048 + fa.T - 1) / fa.T;  // ~2k forward workgroups of 1024 threads, grid-stride beyond
+        if (bx > cap) bx = cap;
+        const int64_t grid = (int64_t)fa.T * (1 + bx);
+        hipLaunchKernelGGL((k_finalize_fwd<LPR, UNR>), dim3((unsigned)grid), dim3(FINFWD_TPB), 0, st, fa, f, (int)bx);
+    });
+    LAUNCH_CHECK();
+    return DQRM_OK;
+}
+
+// The apply of arguments check_apply passed, as `p` plans it; ff.next: the next batch's forward
+// (checked by check_fwd), run where p.form puts it. ws: the merge kernel's positions workspace.
+int run_apply(const ApplyPlan& p, const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
+              const void* payloads, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg, float lr,
+              int mode, int repack_bits, void* ws, const FusedFwd& ff, hipStream_t st) {
+    int rc = 0;
+    ApplyArgs a;
+    a.W = set->W; a.packed = set->packed; a.rowmax = set->rowmax; a.blkmax = set->blkmax;
+    a.sblkmax = set->sblkmax; a.sdirty = set->sdirty; a.pscale = set->pscale; a.meta = set->meta;
+    a.err = set->err; a.cap_base = cap_base; a.cap_total = cap_total;
+    a.payloads = (const unsigned char*)payloads; a.payload_bytes = (int64_t)rank_pitch;  // rank stride
+    a.N = num_ranks; a.T = set->num_tables; a.bits = grad_bits; a.s_avg = s_avg; a.nlr = -lr;
+    a.mode = mode; a.repack = repack_bits == 4; a.bdirty = set->bdirty; a.tmax = set->tmax; a.sync = set->sync;
+    a.fin_launch = p.fin != ApplyFin::Inside;
+    const bool flat = p.kernel >= ApplyKernel::Flat;
+    a.wt = flat ? !a.fin_launch : 1;
+    const int D = set->dim;
+    switch (p.kernel) {
+    case ApplyKernel::Merge: {
+        dqrm_internal::MergeApplyArgs r{};
+        r.W = a.W; r.packed = a.packed; r.rowmax = a.rowmax; r.blkmax = a.blkmax; r.sblkmax = a.sblkmax;
+        r.sdirty = a.sdirty; r.bdirty = a.bdirty; r.tmax = a.tmax; r.sync = a.sync; r.pscale = a.pscale;
+        r.meta = a.meta; r.err = a.err; r.cap_base = cap_base; r.cap_total = cap_total; r.payloads = a.payloads;
+        r.rank_pitch = (int64_t)rank_pitch; r.N = num_ranks; r.T = a.T; r.D = D; r.bits = grad_bits; r.s_avg = s_avg;
+        r.nlr = -lr; r.mode = mode; r.repack = a.repack;
+        merge_chunks(set, cap_total, num_ranks, r.kt, r.kbase);
+        r.pos = reinterpret_cast<int32_t*>(ws);
+        r.diag = dqrm_internal::env_merge_diag();
+        r.gx = merge_apply_gx(set, cap_total, num_ranks, D);
+        if (p.form == DQRM_APPLY_FWD_ONE_LAUNCH) {  // the grid's last T * fwd_gx workgroups, behind each table's gate
+            const dqrm_batch* nb = ff.next;
+            r.fwd_idx = nb->idx; r.fwd_B = nb->num_bags; r.fwd_out = ff.out; r.fwd_ost_t = ff.ost_t; r.fwd_ost_b = ff.ost_b;
+            r.fwd_scale = set->scale; r.fwd_bits = ff.bits; r.fwd_flags = ff.flags;
+            r.fwd_gx = dqrm_internal::merge_forward_gx(nb->num_bags); r.spin_limit = dqrm_internal::env_gate_spin();
+        }
+        DQRM_HIP_TRY(dqrm_internal::launch_apply_merge(r, st));
+        break;
+    }
+    case ApplyKernel::Ranges: {
+        // chunks per slot: the payload capacity of all ranks spread over the slots, ~48
+        // entries per workgroup (at least 1, at most 64)
+        const int64_t slots = (int64_t)a.T * SPLIT;
+        int64_t K = ((int64_t)num_ranks * cap_total + slots * 48 - 1) / (slots * 48);
+        K = K < 1 ? 1 : (K > 64 ? 64 : K);
+        dqrm_internal::RangeApplyArgs r{a.W, a.packed, a.rowmax, a.blkmax, a.sblkmax, a.sdirty, a.bdirty, a.tmax,
+                                        a.sync, a.pscale, a.meta, a.err, cap_base, cap_total, a.payloads,
+                                        (int64_t)rank_pitch, num_ranks, a.T, D, grad_bits, s_avg, -lr, mode,
+                                        a.repack, (int)K};
+        DQRM_HIP_TRY(dqrm_internal::launch_apply_ranges(r, st));
+        break;
+    }
+    case ApplyKernel::Slot:
+        DISPATCH_LPR(D, {
+            if ((rc = allow_lds(k_table_apply<LPR>, SLOT_LDS))) return rc;
+            hipLaunchKernelGGL(k_table_apply<LPR>, dim3(a.T * SPLIT), dim3(TWG), SLOT_LDS, st, a);
+        });
+        LAUNCH_CHECK();
+        break;
+    default:  // the flat kernels
+        // grid (entry chunks, tables, ranks): twice the chunks of an average table (the
+        // per-table capacities live on the device); larger tables grid-stride, chunks past
+        // a table's count exit at once
+        DISPATCH_LPR(D, {
+            constexpr int G = FLAT_TPB / LPR;
+            int64_t gx = 2 * ((cap_total + (int64_t)a.T * G - 1) / ((int64_t)a.T * G));
+            const int64_t lim = (32768 + (int64_t)a.T * num_ranks - 1) / ((int64_t)a.T * num_ranks);
+            if (gx > lim) gx = lim;
+            if (gx < 1) gx = 1;
+            const dim3 grid((unsigned)gx, (unsigned)a.T, (unsigned)num_ranks);
+            if (p.kernel == ApplyKernel::Flat4)
+                hipLaunchKernelGGL((k_apply_flat2<LPR, (LPR >= 4 ? 4 : 2)>), grid, dim3(FLAT_TPB), 0, st, a);
+            else if (p.kernel == ApplyKernel::Flat2)
+                hipLaunchKernelGGL((k_apply_flat2<LPR, 2>), grid, dim3(FLAT_TPB), 0, st, a);
+            else if (a.fin_launch)
+                hipLaunchKernelGGL((k_apply_flat<LPR, false>), grid, dim3(FLAT_TPB), 0, st, a);
+            else
+                hipLaunchKernelGGL((k_apply_flat<LPR, true>), grid, dim3(FLAT_TPB), 0, st, a);
+        });
+        LAUNCH_CHECK();
+    }
+    if (p.fin == ApplyFin::WithFwd) return launch_finalize_fwd(set, fwd_args(set, ff), st);
+    if (p.fin == ApplyFin::Launch && (rc = launch_finalize(set, st, flat, flat))) return rc;
+    if (ff.next && p.form == DQRM_APPLY_FWD_SEPARATE) return launch_fwd(set, ff, st);
+    return DQRM_OK;
+}
+
+// dqrm_emb_bwd_apply_local (ff.next == nullptr) and dqrm_emb_bwd_apply_fwd_local, whose next
+// forward check_fwd passed; both report under the first one's name
+int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
+                    int64_t dy_stride_b, int ste, const int64_t* ws_cap_base, int64_t ws_cap_total,
+                    int32_t* ws_rows, float* ws_vals, int32_t* ws_ucount, float* ws_absmax, int grad_bits,
+                    float* s_avg, float lr, int repack_bits, void* workspace, size_t workspace_bytes,
+                    const FusedFwd& ff, void* stream) {
+    const char* who = "dqrm_emb_bwd_apply_local";
+    int rc = check_set(set);
+    if (rc) return rc;
+    if ((rc = check_batch(batch, who))) return rc;
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, who))) return rc;
+    if ((rc = check_slot_ws(ws_cap_base, ws_rows, ws_vals, ws_ucount, ws_absmax, who, s_avg && ws_cap_total >= 0)))
+        return rc;
+    if (grad_bits < 2 || grad_bits > 16)
+        return set_error(DQRM_E_INVALID, "%s: grad_bits must be 2..16 (got %d)", who, grad_bits);
+    if ((rc = check_repack(set, repack_bits, who))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const LocalPlan plan = local_plan(set, batch, ff.next, ff.flags, stream);
+    if (plan.one_launch) {
+        if (batch->num_bags <= 0)  // nothing to update; the next batch's forward still runs
+            return ff.next ? launch_fwd(set, ff, st) : DQRM_OK;
+        dqrm_internal::CoalesceArgs ca{};
+        ca.meta = set->meta; ca.T = set->num_tables; ca.D = set->dim; ca.B = batch->num_bags; ca.idx = batch->idx;
+        ca.dy = dy; ca.dst_t = dy_stride_t; ca.dst_b = dy_stride_b; ca.scale = set->scale; ca.ste = ste;
+        ca.err = set->err; ca.ws_cap_base = ws_cap_base; ca.ws_rows = ws_rows; ca.ws_vals = ws_vals;
+        ca.ws_ucount = ws_ucount; ca.ws_absmax = ws_absmax;
+        dqrm_internal::LocalApplyArgs la{};
+        la.W = set->W; la.packed = set->packed; la.rowmax = set->rowmax; la.blkmax = set->blkmax;
+        la.sblkmax = set->sblkmax; la.sdirty = set->sdirty; la.bdirty = set->bdirty; la.tmax = set->tmax;
+        la.pscale = set->pscale; la.sync = set->sync; la.s_avg = s_avg; la.bits = grad_bits; la.nlr = -lr;
+        la.repack = repack_bits == 4;
+        dqrm_internal::plan_sub_slots(set->num_rows_host, set->num_tables, &la);
+        if (plan.fwd_inside) {
+            la.fwd_idx = ff.next->idx; la.fwd_out = ff.out; la.fwd_ost_t = ff.ost_t; la.fwd_ost_b = ff.ost_b;
+            la.fwd_scale = set->scale; la.fwd_bits = ff.bits; la.fwd_flags = ff.flags;
+        }
+        const hipError_t e = dqrm_internal::launch_coalesce_pool1(ca, &la, st);
+        if (e != hipSuccess)
+            return set_error(DQRM_E_HIP, "dqrm_emb_bwd_apply_local: launch failed: %s (%d)", hipGetErrorString(e), (int)e);
+        return ff.next && !plan.fwd_inside ? launch_fwd(set, ff, st) : DQRM_OK;
+    }
+    if ((rc = dqrm_emb_bwd_coalesce(set, batch, dy, dy_stride_t, dy_stride_b, ste, ws_cap_base, ws_rows, ws_vals,
+                                    ws_ucount, ws_absmax, workspace, workspace_bytes, stream)))
+        return rc;
+    if ((rc = dqrm_apply_local(set, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount, ws_absmax, grad_bits,
+                               s_avg, lr, repack_bits, stream)))
+        return rc;
+    return ff.next ? launch_fwd(set, ff, st) : DQRM_OK;
+}
+
 }  // namespace
+
+int dqrm_internal::emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, int bits,
+                             uint32_t fwd_flags, int repack_bits, int training, const char* who) {
+    int rc = check_set(set);
+    if (rc) return rc;
+    if (!(fwd_flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
+        return set_error(DQRM_E_INVALID, "%s: embedding_bit %d unsupported", who, bits);
+    if ((fwd_flags & DQRM_FWD_USE_PACKED) && (!set->packed || bits != 4))
+        return set_error(DQRM_E_INVALID, "%s: packed path needs packed rows and bits == 4", who);
+    if ((rc = check_repack(set, repack_bits, who))) return rc;
+    if (!batch) return DQRM_OK;
+    if ((rc = check_batch(batch, who))) return rc;
+    if (next && (rc = check_batch(next, who))) return rc;
+    if (!training) return DQRM_OK;
+    if (bwd_lookup_cap(batch) > 0x3fffffffll)
+        return set_error(DQRM_E_CAPACITY, "%s: max_lookups %lld too large", who, (long long)bwd_lookup_cap(batch));
+    if (set->total_rows > 0xffffffffll) return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 rows", who);
+    return DQRM_OK;
+}
+
+int dqrm_internal::emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
+                                        uint32_t fwd_flags) {
+    return sgd_plan(set, batch, next, fwd_flags).launches;
+}
 
 // ======================================================================================
 // C ABI
@@ -4480,77 +5011,17 @@ int dqrm_refresh_scale_and_pack(const dqrm_table_set* set, int bits, void* strea
     return DQRM_OK;
 }
 
-// the forward's argument checks and kernel arguments (shared by the two forward entry points)
-static int fwd_args(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags, float* out,
-                    int64_t out_stride_t, int64_t out_stride_b, const char* who, FwdArgs* a) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    if (!batch || !batch->idx || !batch->off || !batch->idx_base || !out)
-        return set_error(DQRM_E_INVALID, "%s: null batch/out pointer", who);
-    if (!(flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
-        return set_error(DQRM_E_INVALID, "%s: embedding_bit %d unsupported", who, bits);
-    if ((flags & DQRM_FWD_USE_PACKED) && (!set->packed || bits != 4))
-        return set_error(DQRM_E_INVALID, "%s: packed path needs packed rows and bits == 4", who);
-    if ((((uintptr_t)out) & 15) || (out_stride_t & 3) || (out_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: out must be 16-B aligned with strides %% 4 == 0", who);
-    a->W = set->W; a->packed = set->packed; a->tmax = set->tmax; a->scale = set->scale;
-    a->meta = set->meta; a->err = set->err;
-    a->idx = batch->idx; a->off = batch->off; a->idx_base = batch->idx_base;
-    a->pool1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
-    a->out = out; a->B = batch->num_bags; a->ost_t = out_stride_t; a->ost_b = out_stride_b;
-    a->T = set->num_tables; a->bits = bits; a->flags = flags;
-    a->wt = dqrm_internal::wt_stores(set->dim);
-    return DQRM_OK;
-}
-
 int dqrm_emb_fwd(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags,
                  float* out, int64_t out_stride_t, int64_t out_stride_b, void* stream) {
-    FwdArgs a;
-    int rc = fwd_args(set, batch, bits, flags, out, out_stride_t, out_stride_b, "dqrm_emb_fwd", &a);
+    int rc = check_fwd(set, batch, bits, flags, out, out_stride_t, out_stride_b, "dqrm_emb_fwd");
     if (rc) return rc;
-    if (batch->num_bags <= 0) return DQRM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int D = set->dim;
-    const bool packed_path = (flags & DQRM_FWD_USE_PACKED) && !(flags & DQRM_FWD_FULL_PRECISION) && D >= 8;
-    if (packed_path) {
-        int64_t bx = (a.B + 255) / 256;
-        const int64_t cap = (16384 + a.T - 1) / a.T;
-        if (bx > cap) bx = cap;
-        const bool nt = (flags & DQRM_FWD_NT_STORE) != 0;
-        // y goes write-through only while the eight XCD L2s (32 MB) could hold all of it dirty at
-        // the kernel's end. A larger output is evicted as the kernel runs, the end's write-back
-        // is bounded by L2's size whatever the store, and the plain stream is what the 436 MB
-        // int4_gather line was tuned and measured with: kept. (The cut-off is reasoned; a
-        // write-through run of that line was not made.)
-        if ((int64_t)a.T * a.B * D * (int64_t)sizeof(float) > (32ll << 20)) a.wt &= ~WT_Y;
-        DISPATCH_LPR(D, {
-            if constexpr (LPR >= 2) {
-                if (nt)
-                    hipLaunchKernelGGL((k_emb_fwd_packed<LPR, true>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
-                else
-                    hipLaunchKernelGGL((k_emb_fwd_packed<LPR, false>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
-            }
-        });
-        LAUNCH_CHECK();
-        return DQRM_OK;
-    }
-    DISPATCH_LPR(D, {
-        constexpr int UNR = 4;
-        constexpr int BAGS_PER_WG = (256 / LPR) * UNR;
-        int64_t bx = (a.B + BAGS_PER_WG - 1) / BAGS_PER_WG;
-        const int64_t cap = (8192 + a.T - 1) / a.T;  // ~8k workgroups in total, grid-stride beyond
-        if (bx > cap) bx = cap;
-        hipLaunchKernelGGL((k_emb_fwd<LPR, UNR>), dim3((unsigned)bx, (unsigned)a.T), dim3(256), 0, st, a);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
+    return launch_fwd(set, FusedFwd{batch, bits, flags, out, out_stride_t, out_stride_b}, (hipStream_t)stream);
 }
 
 int dqrm_emb_fwd_after_update(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags,
                               float* out, int64_t out_stride_t, int64_t out_stride_b, const int64_t* rows,
                               int64_t n, int repack_bits, void* stream) {
-    FwdArgs a;
-    int rc = fwd_args(set, batch, bits, flags, out, out_stride_t, out_stride_b, "dqrm_emb_fwd_after_update", &a);
+    int rc = check_fwd(set, batch, bits, flags, out, out_stride_t, out_stride_b, "dqrm_emb_fwd_after_update");
     if (rc) return rc;
     if (n < 0 || (n > 0 && !rows))
         return set_error(DQRM_E_INVALID, "%s: bad row list", "dqrm_emb_fwd_after_update");
@@ -4558,25 +5029,18 @@ int dqrm_emb_fwd_after_update(const dqrm_table_set* set, const dqrm_batch* batch
     const int lpr = set->dim / 4;
     const bool one = n > 0 && n <= 4096 && set->num_tables == 1 && repack_bits == 0 &&
                      !(flags & DQRM_FWD_USE_PACKED) && batch->num_bags > 0 &&
-                     batch->num_bags * (int64_t)lpr <= 16 * 256 && finalize_mode() != 1;
+                     batch->num_bags * (int64_t)lpr <= 16 * 256 && env_finalize() != 1;
     if (!one) {  // the two calls
         if (n > 0 && (rc = dqrm_rows_changed(set, rows, n, repack_bits, stream))) return rc;
         return dqrm_emb_fwd(set, batch, bits, flags, out, out_stride_t, out_stride_b, stream);
     }
     hipStream_t st = (hipStream_t)stream;
+    const FwdArgs a = fwd_args(set, FusedFwd{batch, bits, flags, out, out_stride_t, out_stride_b});
     DISPATCH_LPR(set->dim, {
         hipLaunchKernelGGL((k_fwd_after_update<LPR>), dim3(1), dim3(256), 0, st, a, set->rowmax, set->bdirty,
                            set->sdirty, set->blkmax, set->sblkmax, set->tmax, rows, n, set->total_rows);
     });
     LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-static int check_batch(const dqrm_batch* batch, const char* who) {
-    if (!batch || !batch->idx || !batch->off || !batch->idx_base)
-        return set_error(DQRM_E_INVALID, "%s: null batch pointer", who);
-    if (batch->num_bags > 0xFFFFFFFFll)
-        return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 bags", who);
     return DQRM_OK;
 }
 
@@ -4591,10 +5055,8 @@ int dqrm_emb_bwd_sgd(const dqrm_table_set* set, const dqrm_batch* batch, const f
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_bwd_sgd"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", "dqrm_emb_bwd_sgd");
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_emb_bwd_sgd", repack_bits);
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_sgd"))) return rc;
+    if ((rc = check_repack(set, repack_bits, "dqrm_emb_bwd_sgd"))) return rc;
     if (batch->num_bags <= 0) return DQRM_OK;
     BwdCall c{};
     c.set = set; c.batch = batch; c.dy = dy; c.dst_t = dy_stride_t; c.dst_b = dy_stride_b; c.ste = ste;
@@ -4609,21 +5071,16 @@ int dqrm_emb_bwd_sgd_fwd(const dqrm_table_set* set, const dqrm_batch* batch, con
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_bwd_sgd_fwd"))) return rc;
-    FwdArgs fa;  // the forward's arguments, validated as dqrm_emb_fwd validates them
-    if ((rc = fwd_args(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, "dqrm_emb_bwd_sgd_fwd", &fa)))
+    if ((rc = check_fwd(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, "dqrm_emb_bwd_sgd_fwd")))
         return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", "dqrm_emb_bwd_sgd_fwd");
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_emb_bwd_sgd_fwd",
-                         repack_bits);
-    if (batch->num_bags <= 0)
-        return dqrm_emb_fwd(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, stream);
+    const FusedFwd ff{next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b};
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_sgd_fwd"))) return rc;
+    if ((rc = check_repack(set, repack_bits, "dqrm_emb_bwd_sgd_fwd"))) return rc;
+    if (batch->num_bags <= 0) return launch_fwd(set, ff, (hipStream_t)stream);
     BwdCall c{};
     c.set = set; c.batch = batch; c.dy = dy; c.dst_t = dy_stride_t; c.dst_b = dy_stride_b; c.ste = ste;
     c.lr = lr; c.repack = repack_bits == 4; c.ws = workspace; c.ws_bytes = workspace_bytes;
-    c.next = next; c.fwd_bits = fwd_bits; c.fwd_flags = fwd_flags; c.fwd_out = out;
-    c.fwd_ost_t = out_stride_t; c.fwd_ost_b = out_stride_b;
+    c.fwd = ff;
     return launch_bwd<0>(c, (hipStream_t)stream, "dqrm_emb_bwd_sgd_fwd");
 }
 
@@ -4631,15 +5088,13 @@ int dqrm_rows_changed(const dqrm_table_set* set, const int64_t* rows, int64_t n,
     int rc = check_set(set);
     if (rc) return rc;
     if (n < 0 || (n > 0 && !rows)) return set_error(DQRM_E_INVALID, "%s: bad row list", "dqrm_rows_changed");
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_rows_changed",
-                         repack_bits);
+    if ((rc = check_repack(set, repack_bits, "dqrm_rows_changed"))) return rc;
     if (n == 0) return DQRM_OK;
     hipStream_t st = (hipStream_t)stream;
     uint8_t* pk = repack_bits == 4 ? set->packed : nullptr;
     // a one-table set finalizes inside the launch (its last workgroup); larger sets launch
     // the per-table finalize
-    const bool fin = set->num_tables == 1 && finalize_mode() != 1;
+    const bool fin = set->num_tables == 1 && env_finalize() != 1;
     const RcFin rf{set->blkmax, set->sblkmax, set->tmax, set->sync};
     DISPATCH_LPR(set->dim, {
         constexpr int G = 256 / LPR;
@@ -4662,9 +5117,7 @@ int dqrm_emb_bwd_lookup_grad(const dqrm_table_set* set, const dqrm_batch* batch,
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_bwd_lookup_grad"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0",
-                         "dqrm_emb_bwd_lookup_grad");
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_lookup_grad"))) return rc;
     if (!rows || !vals || (((uintptr_t)vals) & 15))
         return set_error(DQRM_E_INVALID, "%s: rows / 16-B aligned vals required", "dqrm_emb_bwd_lookup_grad");
     if (batch->num_bags <= 0) return DQRM_OK;
@@ -4712,17 +5165,13 @@ int dqrm_emb_bwd_coalesce(const dqrm_table_set* set, const dqrm_batch* batch, co
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_bwd_coalesce"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", "dqrm_emb_bwd_coalesce");
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || (((uintptr_t)ws_vals) & 15))
-        return set_error(DQRM_E_INVALID, "%s: null/unaligned workspace", "dqrm_emb_bwd_coalesce");
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_coalesce"))) return rc;
+    if ((rc = check_slot_ws(ws_cap_base, ws_rows, ws_vals, ws_ucount, ws_absmax, "dqrm_emb_bwd_coalesce"))) return rc;
     BwdCall c{};
     c.set = set; c.batch = batch; c.dy = dy; c.dst_t = dy_stride_t; c.dst_b = dy_stride_b; c.ste = ste;
     c.ws_cap_base = ws_cap_base; c.ws_rows = ws_rows; c.ws_vals = ws_vals; c.ws_ucount = ws_ucount;
     c.ws_absmax = ws_absmax; c.ws = workspace; c.ws_bytes = workspace_bytes;
-    if (g_coalesce_kernel.load() == DQRM_COALESCE_AUTO && (batch->flags & DQRM_BATCH_POOLING_ONE) &&
-        batch->num_bags <= dqrm_internal::kCoalesceMaxB && batch->max_lookups >= batch->num_bags &&
-        set->total_rows <= 0xffffffffll) {
+    if (coalesce_takes_pool1(set, batch)) {
         dqrm_internal::CoalesceArgs ca{};
         ca.meta = set->meta; ca.T = set->num_tables; ca.D = set->dim; ca.B = batch->num_bags; ca.idx = batch->idx;
         ca.dy = dy; ca.dst_t = dy_stride_t; ca.dst_b = dy_stride_b; ca.scale = set->scale; ca.ste = ste;
@@ -4747,11 +5196,8 @@ int dqrm_emb_bwd_coalesce_scaled(const dqrm_table_set* set, const dqrm_batch* ba
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_bwd_coalesce_scaled"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0",
-                         "dqrm_emb_bwd_coalesce_scaled");
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || (((uintptr_t)ws_vals) & 15))
-        return set_error(DQRM_E_INVALID, "%s: null/unaligned workspace", "dqrm_emb_bwd_coalesce_scaled");
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_coalesce_scaled"))) return rc;
+    if ((rc = check_slot_ws(ws_cap_base, ws_rows, ws_vals, ws_ucount, ws_absmax, "dqrm_emb_bwd_coalesce_scaled"))) return rc;
     BwdCall c{};
     c.set = set; c.batch = batch; c.dy = dy; c.dst_t = dy_stride_t; c.dst_b = dy_stride_b; c.ste = ste;
     c.ws_cap_base = ws_cap_base; c.ws_rows = ws_rows; c.ws_vals = ws_vals; c.ws_ucount = ws_ucount;
@@ -4781,11 +5227,7 @@ int dqrm_grad_quant_pack_strided(int num_tables, int dim, const int64_t* ws_cap_
     if (((uintptr_t)payload) & 15)
         return set_error(DQRM_E_INVALID, "%s: payload must be 16-B aligned", "dqrm_grad_quant_pack");
     hipStream_t st = (hipStream_t)stream;
-    static const bool legacy = [] {  // DQRM_QPACK=legacy: the one-workgroup-per-slot kernel (A/B)
-        const char* e = getenv("DQRM_QPACK");
-        return e && !strcmp(e, "legacy");
-    }();
-    if (!legacy) {
+    if (!dqrm_internal::env_qpack_legacy()) {  // (legacy: the one-workgroup-per-slot kernel, A/B)
         dqrm_internal::QuantPackArgs q{num_tables, dim, ws_cap_base, ws_rows, ws_vals, ws_ucount, absmax_all,
                                        absmax_pitch, num_ranks, grad_bits, cap_base, cap_total, s_avg,
                                        (unsigned char*)payload};
@@ -4836,10 +5278,8 @@ int dqrm_emb_local_update(const dqrm_table_set* set, const dqrm_batch* batch, co
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_emb_local_update"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", "dqrm_emb_local_update");
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_emb_local_update", repack_bits);
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_local_update"))) return rc;
+    if ((rc = check_repack(set, repack_bits, "dqrm_emb_local_update"))) return rc;
     if (batch->num_bags <= 0) return DQRM_OK;
     BwdCall c{};
     c.set = set; c.batch = batch; c.dy = dy; c.dst_t = dy_stride_t; c.dst_b = dy_stride_b; c.ste = ste;
@@ -4847,158 +5287,9 @@ int dqrm_emb_local_update(const dqrm_table_set* set, const dqrm_batch* batch, co
     return launch_bwd<2>(c, (hipStream_t)stream, "dqrm_emb_local_update");
 }
 
-// recover the per-rank batch B from cap_total = sum_t min(B, n_t) (host row counts), -1 without them
-static int64_t recover_batch(const dqrm_table_set* set, int64_t cap_total) {
-    const int64_t* nr = set->num_rows_host;
-    if (!nr) return -1;
-    int64_t lo = 0, hi = 0;
-    for (int t = 0; t < set->num_tables; ++t) hi = nr[t] > hi ? nr[t] : hi;
-    while (lo < hi) {  // smallest B with sum_t min(B, n_t) >= cap_total
-        const int64_t mid = (lo + hi) / 2;
-        int64_t c = 0;
-        for (int t = 0; t < set->num_tables; ++t) c += nr[t] < mid ? nr[t] : mid;
-        if (c < cap_total) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// k_apply_pos: entry chunks per (table, rank) -- one pass of 4 entries per lane group covers the
-// largest table's capacity min(B, n_t) -- at most 32768 workgroups
-static int merge_apply_gx(const dqrm_table_set* set, int64_t cap_total, int num_ranks, int D) {
-    const int64_t per = (256 / (D / 4)) * 4;  // entries per workgroup: (lane groups) x AP_INFL
-    const int64_t B = recover_batch(set, cap_total);
-    const int64_t cmax = B >= 0 ? B : cap_total;
-    int64_t gx = (cmax + per - 1) / per;
-    const int64_t lim = (32768 + (int64_t)set->num_tables * num_ranks - 1) / ((int64_t)set->num_tables * num_ranks);
-    gx = gx > lim ? lim : gx;
-    return (int)(gx < 1 ? 1 : gx);
-}
-
-// Chunks per row-range slot of each table for k_apply_merge: about DQRM_MERGE_KEYS (default 256)
-// payload entries of all ranks per workgroup, from the table's payload capacity min(B, n_t)
-// (B recovered from cap_total = sum_t min(B, n_t) and the host row counts; without those, an
-// even split), at most the slot's blocks (chunks are block-aligned) and at most 64.
-static void merge_plan(const dqrm_table_set* set, int64_t cap_total, int N, int* kt, int* kbase) {
-    static const int64_t target = [] {
-        const char* e = getenv("DQRM_MERGE_KEYS");
-        const long v = e ? atol(e) : 256;
-        return (int64_t)(v > 0 ? v : 256);
-    }();
-    const int T = set->num_tables;
-    const int64_t* nr = set->num_rows_host;
-    int64_t B = -1;
-    if (nr) {  // smallest B with sum_t min(B, n_t) >= cap_total
-        int64_t lo = 0, hi = 0;
-        for (int t = 0; t < T; ++t) hi = nr[t] > hi ? nr[t] : hi;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) / 2;
-            int64_t c = 0;
-            for (int t = 0; t < T; ++t) c += nr[t] < mid ? nr[t] : mid;
-            if (c < cap_total) lo = mid + 1; else hi = mid;
-        }
-        B = lo;
-    }
-    kbase[0] = 0;
-    for (int t = 0; t < T; ++t) {
-        const int64_t cap_t = B >= 0 ? (nr[t] < B ? nr[t] : B) : (cap_total + T - 1) / T;
-        int64_t K = ((int64_t)N * cap_t + SPLIT * target - 1) / (SPLIT * target);
-        if (nr) {
-            const int64_t blocks_per_slot = ((nr[t] + BLK - 1) / BLK + SPLIT - 1) / SPLIT;
-            K = K < blocks_per_slot ? K : blocks_per_slot;
-        }
-        K = K < 1 ? 1 : (K > 64 ? 64 : K);
-        kt[t] = (int)K;
-        kbase[t + 1] = kbase[t] + SPLIT * (int)K;
-    }
-}
-
-static int fwd_args(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags, float* out,
-                    int64_t out_stride_t, int64_t out_stride_b, const char* who, FwdArgs* a);
-
-// the flat apply's finalize launch together with the next forward (k_finalize_fwd): the exact
-// FP32-row forward (the INT4 packed gather stays a launch of its own); DQRM_FIN_FWD=0 turns it off
-static bool finfwd_fits(const dqrm_table_set* set, const dqrm_batch* next, uint32_t flags) {
-    static const bool off = [] {
-        const char* e = getenv("DQRM_FIN_FWD");
-        return e && !strcmp(e, "0");
-    }();
-    const bool packed_path = (flags & DQRM_FWD_USE_PACKED) && !(flags & DQRM_FWD_FULL_PRECISION) && set->dim >= 8;
-    return !off && next && next->num_bags > 0 && !packed_path;
-}
-
-static int launch_finalize_fwd(const dqrm_table_set* set, FwdArgs fa, hipStream_t st) {
-    static const uint32_t spin = [] {  // DQRM_GATE_SPIN: gate polls before a forward flags a stall
-        const char* e = getenv("DQRM_GATE_SPIN");
-        return e ? (uint32_t)strtoul(e, nullptr, 10) : (1u << 20);
-    }();
-    fa.sync = set->sync;
-    fa.spin = spin;
-    FinArgs f{set->W, set->rowmax, set->blkmax, set->sblkmax, set->sdirty, set->bdirty, set->tmax, set->dim,
-              1, fin_flagged_skip() ? 1 : 0};
-    DISPATCH_LPR(set->dim, {
-        constexpr int UNR = 4;
-        constexpr int BAGS_PER_WG = (FINFWD_TPB / LPR) * UNR;
-        int64_t bx = (fa.B + BAGS_PER_WG - 1) / BAGS_PER_WG;
-        const int64_t cap = (2048 + fa.T - 1) / fa.T;  // ~2k forward workgroups of 1024 threads, grid-stride beyond
-        if (bx > cap) bx = cap;
-        const int64_t grid = (int64_t)fa.T * (1 + bx);
-        hipLaunchKernelGGL((k_finalize_fwd<LPR, UNR>), dim3((unsigned)grid), dim3(FINFWD_TPB), 0, st, fa, f, (int)bx);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-// the apply's kernel choice: the merge kernels (with the next batch's forward in the update's
-// launch when nf is given) when DQRM_APPLY=merge / dqrm_set_apply_kernel(DQRM_APPLY_MERGE) and
-// the positions workspace is given (N = 1 needs none). Not AUTO: measured on the TB shape
-// (profiles/r6_apply_ranks_*.txt) it is not faster than the flat kernel + finalize launch at
-// N = 1..8 (2048 per rank: 20.6 / 53.4 / 75.8 / 143 us vs 15.4 / 39.4 / 68.0 / 138.8 us).
-static bool apply_uses_merge(const dqrm_table_set* set, int num_ranks, int64_t cap_total, size_t ws_bytes) {
-    const int kind = apply_kernel_kind();
-    const bool ok = num_ranks <= dqrm_internal::kMergeMaxRanks && set->num_tables <= dqrm_internal::kMergeMaxTables &&
-                    ws_bytes >= dqrm_internal::apply_workspace_bytes(num_ranks, cap_total);
-    return ok && kind == DQRM_APPLY_MERGE;
-}
-
-// the flat kernel takes the apply (the choice apply_update_ex makes below)
-static bool apply_takes_flat(const dqrm_table_set* set, int num_ranks, int64_t cap_total, size_t ws_bytes) {
-    if (apply_uses_merge(set, num_ranks, cap_total, ws_bytes)) return false;
-    const int kind = apply_kernel_kind();
-    if (kind == DQRM_APPLY_RANGES) return false;
-    return !(kind == DQRM_APPLY_SLOT || (kind == DQRM_APPLY_AUTO && num_ranks > 1 && num_ranks >= set->dim / 4));
-}
-
 size_t dqrm_apply_workspace_bytes(int num_ranks, int64_t cap_total) {
     if (num_ranks <= 0 || cap_total < 0) return 0;
     return dqrm_internal::apply_workspace_bytes(num_ranks, cap_total);
-}
-
-// the next batch's forward inside the merge kernel's launch: a Criteo-form batch on the exact
-// FP32 rows (the INT4 packed path stays a launch of its own); DQRM_FUSED_FWD=0 turns it off
-static bool merge_fwd_fits(const dqrm_batch* next, uint32_t flags) {
-    static const bool off = [] {
-        const char* e = getenv("DQRM_FUSED_FWD");
-        return e && !strcmp(e, "0");
-    }();
-    return !off && next && (next->flags & DQRM_BATCH_POOLING_ONE) && next->num_bags > 0 &&
-           next->max_lookups >= next->num_bags && !(flags & DQRM_FWD_USE_PACKED);
-}
-
-static int apply_update(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total, const void* payloads,
-                        size_t payload_bytes, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg,
-                        float lr, int mode, int repack_bits, void* ws, size_t ws_bytes, const FwdArgs* nf,
-                        void* stream);
-static int apply_update_ex(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total, const void* payloads,
-                           size_t payload_bytes, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg,
-                           float lr, int mode, int repack_bits, void* ws, size_t ws_bytes, const FwdArgs* nf,
-                           bool* fin_deferred, void* stream);
-
-int dqrm_apply_sparse_update_strided(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
-                                     const void* payloads, size_t payload_bytes, size_t rank_pitch, int num_ranks,
-                                     int grad_bits, const float* s_avg, float lr, int mode, int repack_bits,
-                                     void* stream) {
-    return apply_update(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits, s_avg,
-                        lr, mode, repack_bits, nullptr, 0, nullptr, stream);
 }
 
 int dqrm_apply_sparse_update_fwd(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
@@ -5009,25 +5300,33 @@ int dqrm_apply_sparse_update_fwd(const dqrm_table_set* set, const int64_t* cap_b
                                  void* stream) {
     if (workspace && (((uintptr_t)workspace) & 15))
         return set_error(DQRM_E_INVALID, "%s: workspace must be 16-B aligned", "dqrm_apply_sparse_update_fwd");
-    if (!next)  // the apply alone, with the workspace
-        return apply_update(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits, s_avg,
-                            lr, mode, repack_bits, workspace, workspace_bytes, nullptr, stream);
-    FwdArgs fa;  // the forward's arguments, validated as dqrm_emb_fwd validates them
-    int rc = fwd_args(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, "dqrm_apply_sparse_update_fwd",
-                      &fa);
-    if (rc) return rc;
-    if (apply_uses_merge(set, num_ranks, cap_total, workspace_bytes) && merge_fwd_fits(next, fwd_flags))
-        return apply_update(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits, s_avg,
-                            lr, mode, repack_bits, workspace, workspace_bytes, &fa, stream);
-    // the flat apply: its finalize and the forward in one launch when the forward takes the exact rows
-    const bool fin_fwd = finfwd_fits(set, next, fwd_flags);
-    bool deferred = false;
-    if ((rc = apply_update_ex(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits,
-                              s_avg, lr, mode, repack_bits, workspace, workspace_bytes, nullptr,
-                              fin_fwd ? &deferred : nullptr, stream)))
+    int rc = 0;  // next == NULL: the apply alone, with the workspace
+    if (next && (rc = check_fwd(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b,
+                                "dqrm_apply_sparse_update_fwd")))
         return rc;
-    if (deferred) return launch_finalize_fwd(set, fa, (hipStream_t)stream);
-    return dqrm_emb_fwd(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, stream);
+    if ((rc = check_apply(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits, s_avg,
+                          mode, repack_bits)))
+        return rc;
+    const ApplyPlan plan = apply_plan(set, num_ranks, cap_total, workspace_bytes, next, fwd_flags);
+    return run_apply(plan, set, cap_base, cap_total, payloads, rank_pitch, num_ranks, grad_bits, s_avg, lr, mode,
+                     repack_bits, workspace, FusedFwd{next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b},
+                     (hipStream_t)stream);
+}
+
+int dqrm_apply_sparse_update_strided(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
+                                     const void* payloads, size_t payload_bytes, size_t rank_pitch, int num_ranks,
+                                     int grad_bits, const float* s_avg, float lr, int mode, int repack_bits,
+                                     void* stream) {
+    return dqrm_apply_sparse_update_fwd(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks,
+                                        grad_bits, s_avg, lr, mode, repack_bits, nullptr, 0, nullptr, 4, 0, nullptr, 0,
+                                        0, stream);
+}
+
+int dqrm_apply_sparse_update(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
+                             const void* payloads, size_t payload_bytes, int num_ranks, int grad_bits,
+                             const float* s_avg, float lr, int mode, int repack_bits, void* stream) {
+    return dqrm_apply_sparse_update_strided(set, cap_base, cap_total, payloads, payload_bytes, payload_bytes,
+                                            num_ranks, grad_bits, s_avg, lr, mode, repack_bits, stream);
 }
 
 int dqrm_apply_fwd_form(const dqrm_table_set* set, int num_ranks, int64_t cap_total, size_t workspace_bytes,
@@ -5037,157 +5336,13 @@ int dqrm_apply_fwd_form(const dqrm_table_set* set, int num_ranks, int64_t cap_to
     if ((rc = check_batch(next, "dqrm_apply_fwd_form"))) return rc;
     if (num_ranks <= 0 || num_ranks > DQRM_MAX_RANKS)
         return set_error(DQRM_E_INVALID, "%s: bad ranks (%d)", "dqrm_apply_fwd_form", num_ranks);
-    if (apply_uses_merge(set, num_ranks, cap_total, workspace_bytes) && merge_fwd_fits(next, fwd_flags))
-        return DQRM_APPLY_FWD_ONE_LAUNCH;
-    if (apply_takes_flat(set, num_ranks, cap_total, workspace_bytes) && finalize_launch_flat() &&
-        finfwd_fits(set, next, fwd_flags))
-        return DQRM_APPLY_FWD_FIN_FWD;
-    return DQRM_APPLY_FWD_SEPARATE;
+    return apply_plan(set, num_ranks, cap_total, workspace_bytes, next, fwd_flags).form;
 }
 
 int dqrm_apply_fwd_is_one_launch(const dqrm_table_set* set, int num_ranks, int64_t cap_total, size_t workspace_bytes,
                                  const dqrm_batch* next, uint32_t fwd_flags) {
     const int f = dqrm_apply_fwd_form(set, num_ranks, cap_total, workspace_bytes, next, fwd_flags);
     return f < 0 ? f : (f == DQRM_APPLY_FWD_ONE_LAUNCH ? 1 : 0);
-}
-
-static int apply_update(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total, const void* payloads,
-                        size_t payload_bytes, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg,
-                        float lr, int mode, int repack_bits, void* ws, size_t ws_bytes, const FwdArgs* nf,
-                        void* stream) {
-    return apply_update_ex(set, cap_base, cap_total, payloads, payload_bytes, rank_pitch, num_ranks, grad_bits, s_avg,
-                           lr, mode, repack_bits, ws, ws_bytes, nf, nullptr, stream);
-}
-
-// fin_deferred (non-null): a flat apply's finalize launch is left to the caller (*fin_deferred = true),
-// which runs it together with the next forward (k_finalize_fwd)
-static int apply_update_ex(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total, const void* payloads,
-                           size_t payload_bytes, size_t rank_pitch, int num_ranks, int grad_bits, const float* s_avg,
-                           float lr, int mode, int repack_bits, void* ws, size_t ws_bytes, const FwdArgs* nf,
-                           bool* fin_deferred, void* stream) {
-    if (fin_deferred) *fin_deferred = false;
-    int rc = check_set(set);
-    if (rc) return rc;
-    if (num_ranks <= 0 || num_ranks > DQRM_MAX_RANKS || !payloads || !cap_base)
-        return set_error(DQRM_E_INVALID, "%s: bad ranks/payloads (%d)", "dqrm_apply_sparse_update", num_ranks);
-    if (mode == DQRM_UPD_FP32 ? grad_bits != 32 : (grad_bits < 2 || grad_bits > 16 || !s_avg))
-        return set_error(DQRM_E_INVALID, "%s: mode/grad_bits mismatch (%d)", "dqrm_apply_sparse_update", grad_bits);
-    if (payload_bytes != dqrm_payload_bytes(set->num_tables, cap_total, set->dim, grad_bits))
-        return set_error(DQRM_E_INVALID, "%s: payload_bytes mismatch", "dqrm_apply_sparse_update");
-    if (rank_pitch < payload_bytes || (rank_pitch & 15) || (((uintptr_t)payloads) & 15))
-        return set_error(DQRM_E_INVALID, "%s: rank pitch %zu / payload alignment", "dqrm_apply_sparse_update",
-                         rank_pitch);
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_apply_sparse_update", repack_bits);
-    ApplyArgs a;
-    a.W = set->W; a.packed = set->packed; a.rowmax = set->rowmax; a.blkmax = set->blkmax;
-    a.sblkmax = set->sblkmax; a.sdirty = set->sdirty; a.pscale = set->pscale; a.meta = set->meta;
-    a.err = set->err; a.cap_base = cap_base; a.cap_total = cap_total;
-    a.payloads = (const unsigned char*)payloads; a.payload_bytes = (int64_t)rank_pitch;  // rank stride
-    a.N = num_ranks; a.T = set->num_tables; a.bits = grad_bits; a.s_avg = s_avg; a.nlr = -lr;
-    a.mode = mode; a.repack = repack_bits == 4; a.bdirty = set->bdirty; a.tmax = set->tmax; a.sync = set->sync;
-    a.fin_launch = finalize_launch(); a.wt = 1;
-    hipStream_t st = (hipStream_t)stream;
-    const int D = set->dim;
-    const int kind = apply_kernel_kind();
-    bool flat = false;
-    // MERGE (AUTO for 1 < N <= 16 ranks, T <= 64 tables): the ranks' rows merged in LDS per
-    // block-aligned row range, the hierarchy finalized in-launch (dqrm_apply_merge.hip)
-    if (apply_uses_merge(set, num_ranks, cap_total, ws_bytes)) {
-        dqrm_internal::MergeApplyArgs r{};
-        r.W = a.W; r.packed = a.packed; r.rowmax = a.rowmax; r.blkmax = a.blkmax; r.sblkmax = a.sblkmax;
-        r.sdirty = a.sdirty; r.bdirty = a.bdirty; r.tmax = a.tmax; r.sync = a.sync; r.pscale = a.pscale;
-        r.meta = a.meta; r.err = a.err; r.cap_base = cap_base; r.cap_total = cap_total; r.payloads = a.payloads;
-        r.rank_pitch = (int64_t)rank_pitch; r.N = num_ranks; r.T = a.T; r.D = D; r.bits = grad_bits; r.s_avg = s_avg;
-        r.nlr = -lr; r.mode = mode; r.repack = a.repack;
-        merge_plan(set, cap_total, num_ranks, r.kt, r.kbase);
-        r.pos = reinterpret_cast<int32_t*>(ws);
-        static const int diag = [] {  // timing experiments: phases of k_merge_pos skipped (results wrong)
-            const char* e = getenv("DQRM_MERGE_DIAG");
-            return e ? atoi(e) : 0;
-        }();
-        r.diag = diag;
-        r.gx = merge_apply_gx(set, cap_total, num_ranks, D);
-        if (nf) {  // the next batch's forward: the grid's last T * fwd_gx workgroups, behind each table's gate
-            static const uint32_t spin = [] {  // DQRM_GATE_SPIN: gate polls before a forward flags a stall
-                const char* e = getenv("DQRM_GATE_SPIN");
-                return e ? (uint32_t)strtoul(e, nullptr, 10) : (1u << 20);
-            }();
-            r.fwd_idx = nf->idx; r.fwd_B = nf->B; r.fwd_out = nf->out; r.fwd_ost_t = nf->ost_t; r.fwd_ost_b = nf->ost_b;
-            r.fwd_scale = set->scale; r.fwd_bits = nf->bits; r.fwd_flags = nf->flags;
-            r.fwd_gx = dqrm_internal::merge_forward_gx(nf->B); r.spin_limit = spin;
-        }
-        DQRM_HIP_TRY(dqrm_internal::launch_apply_merge(r, st));
-        return DQRM_OK;  // the |W| hierarchy is finalized inside the launch
-    }
-    if (nf) return set_error(DQRM_E_INVALID, "%s: a fused forward needs the merge kernel", "dqrm_apply_sparse_update");
-    if (kind == DQRM_APPLY_RANGES) {
-        // chunks per slot: the payload capacity of all ranks spread over the slots, ~48
-        // entries per workgroup (at least 1, at most 64)
-        const int64_t slots = (int64_t)a.T * SPLIT;
-        int64_t K = ((int64_t)num_ranks * cap_total + slots * 48 - 1) / (slots * 48);
-        K = K < 1 ? 1 : (K > 64 ? 64 : K);
-        dqrm_internal::RangeApplyArgs r{a.W, a.packed, a.rowmax, a.blkmax, a.sblkmax, a.sdirty, a.bdirty, a.tmax,
-                                        a.sync, a.pscale, a.meta, a.err, cap_base, cap_total, a.payloads,
-                                        (int64_t)rank_pitch, num_ranks, a.T, D, grad_bits, s_avg, -lr, mode,
-                                        a.repack, (int)K};
-        DQRM_HIP_TRY(dqrm_internal::launch_apply_ranges(r, st));
-        return DQRM_OK;  // the |W| hierarchy is finalized inside the launch
-    }
-    // AUTO: flat while each lane of a row's group searches at most one other rank
-    // (num_ranks < D/4), slot beyond (tools/bench_apply_ranks.py, DESIGN.md section 8)
-    if (!apply_takes_flat(set, num_ranks, cap_total, ws_bytes)) {  // SLOT, or AUTO at num_ranks >= D/4
-        DISPATCH_LPR(D, {
-            if ((rc = allow_lds(k_table_apply<LPR>, SLOT_LDS))) return rc;
-            hipLaunchKernelGGL(k_table_apply<LPR>, dim3(a.T * SPLIT), dim3(TWG), SLOT_LDS, st, a);
-        });
-    } else {
-        flat = true;
-        a.fin_launch = finalize_launch_flat();
-        a.wt = !a.fin_launch;
-        // grid (entry chunks, tables, ranks): twice the chunks of an average table (the
-        // per-table capacities live on the device); larger tables grid-stride, chunks past
-        // a table's count exit at once
-        DISPATCH_LPR(D, {
-            constexpr int G = FLAT_TPB / LPR;
-            int64_t gx = 2 * ((cap_total + (int64_t)a.T * G - 1) / ((int64_t)a.T * G));
-            const int64_t lim = (32768 + (int64_t)a.T * num_ranks - 1) / ((int64_t)a.T * num_ranks);
-            if (gx > lim) gx = lim;
-            if (gx < 1) gx = 1;
-            // two entries per lane group when the tables hold enough entries to keep the chip busy
-            // at half the workgroups (same box, TB: 2048 per rank 129 vs 142 us at N = 8, 44 vs 48 at
-            // N = 2; 256 per rank slower: 20 vs 14 us at N = 2); DQRM_FLAT_DUAL=0/1 forces it
-            const char* dual_e = getenv("DQRM_FLAT_DUAL");  // read per call (tests switch it)
-            const int dual_env = dual_e ? atoi(dual_e) : -1;
-            const bool dual = dual_env >= 0 ? dual_env != 0 : cap_total >= (int64_t)512 * a.T;
-            if (a.fin_launch && dual && num_ranks > 1 && num_ranks <= FLAT_HDR_RANKS && dual_env == 4)
-                hipLaunchKernelGGL((k_apply_flat2<LPR, (LPR >= 4 ? 4 : 2)>), dim3((unsigned)gx, (unsigned)a.T,
-                                   (unsigned)num_ranks), dim3(FLAT_TPB), 0, st, a);  // (LDS: E = 4 needs LPR >= 4)
-            else if (a.fin_launch && dual && num_ranks > 1 && num_ranks <= FLAT_HDR_RANKS)
-                hipLaunchKernelGGL((k_apply_flat2<LPR, 2>), dim3((unsigned)gx, (unsigned)a.T, (unsigned)num_ranks),
-                                   dim3(FLAT_TPB), 0, st, a);
-            else if (a.fin_launch)
-                hipLaunchKernelGGL((k_apply_flat<LPR, false>), dim3((unsigned)gx, (unsigned)a.T, (unsigned)num_ranks),
-                                   dim3(FLAT_TPB), 0, st, a);
-            else
-                hipLaunchKernelGGL((k_apply_flat<LPR, true>), dim3((unsigned)gx, (unsigned)a.T, (unsigned)num_ranks),
-                                   dim3(FLAT_TPB), 0, st, a);
-        });
-    }
-    LAUNCH_CHECK();  // both kernels finalize the |W| hierarchy inside the launch
-    if (a.fin_launch && flat && fin_deferred) {
-        *fin_deferred = true;
-        return DQRM_OK;
-    }
-    if (a.fin_launch) return launch_finalize(set, st, flat, flat);
-    return DQRM_OK;
-}
-
-int dqrm_apply_sparse_update(const dqrm_table_set* set, const int64_t* cap_base, int64_t cap_total,
-                             const void* payloads, size_t payload_bytes, int num_ranks, int grad_bits,
-                             const float* s_avg, float lr, int mode, int repack_bits, void* stream) {
-    return dqrm_apply_sparse_update_strided(set, cap_base, cap_total, payloads, payload_bytes, payload_bytes,
-                                            num_ranks, grad_bits, s_avg, lr, mode, repack_bits, stream);
 }
 
 int dqrm_apply_local(const dqrm_table_set* set, const int64_t* ws_cap_base, int64_t ws_cap_total,
@@ -5200,8 +5355,7 @@ int dqrm_apply_local(const dqrm_table_set* set, const int64_t* ws_cap_base, int6
         return set_error(DQRM_E_INVALID, "%s: grad_bits must be 2..16 (got %d)", "dqrm_apply_local", grad_bits);
     if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || !s_avg || ws_cap_total < 0)
         return set_error(DQRM_E_INVALID, "%s: null workspace pointer", "dqrm_apply_local");
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", "dqrm_apply_local", repack_bits);
+    if ((rc = check_repack(set, repack_bits, "dqrm_apply_local"))) return rc;
     ApplyArgs a{};
     a.W = set->W; a.packed = set->packed; a.rowmax = set->rowmax; a.blkmax = set->blkmax;
     a.sblkmax = set->sblkmax; a.sdirty = set->sdirty; a.bdirty = set->bdirty; a.tmax = set->tmax; a.pscale = set->pscale;
@@ -5231,51 +5385,12 @@ int dqrm_apply_local(const dqrm_table_set* set, const int64_t* ws_cap_base, int6
     return DQRM_OK;
 }
 
-// dqrm_emb_bwd_apply_local's choice: one launch for Criteo-form batches whose grid can be
-// resident at once (device CUs, occupancy, the stream's CU mask), the two calls otherwise
-static bool apply_local_one_launch(const dqrm_table_set* set, const dqrm_batch* batch, void* stream) {
-    static const bool fused_off = [] {
-        const char* e = getenv("DQRM_LOCAL_FUSED");
-        return e && !strcmp(e, "0");
-    }();
-    return !fused_off && g_coalesce_kernel.load() == DQRM_COALESCE_AUTO && (batch->flags & DQRM_BATCH_POOLING_ONE) &&
-           batch->num_bags <= dqrm_internal::kCoalesceMaxB && batch->max_lookups >= batch->num_bags &&
-           set->total_rows <= 0xffffffffll && set->num_tables <= dqrm_internal::kCoalesceApplyMaxT &&
-           dqrm_internal::coalesce_apply_resident(set->num_tables, (hipStream_t)stream);
-}
-
-// the next batch's forward runs inside the one-launch step when it is a Criteo-form batch of
-// the same size on the exact FP32 rows (the INT4 packed path stays a launch of its own)
-static bool fused_fwd_fits(const dqrm_batch* batch, const dqrm_batch* next, uint32_t flags) {
-    static const bool off = [] {
-        const char* e = getenv("DQRM_FUSED_FWD");
-        return e && !strcmp(e, "0");
-    }();
-    return !off && next && (next->flags & DQRM_BATCH_POOLING_ONE) && next->num_bags == batch->num_bags &&
-           next->max_lookups >= next->num_bags && !(flags & DQRM_FWD_USE_PACKED);
-}
-
 int dqrm_bwd_apply_local_is_one_launch(const dqrm_table_set* set, const dqrm_batch* batch, void* stream) {
     int rc = check_set(set);
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_bwd_apply_local_is_one_launch"))) return rc;
-    return apply_local_one_launch(set, batch, stream) ? 1 : 0;
+    return local_plan(set, batch, nullptr, 0, stream).one_launch ? 1 : 0;
 }
-
-// The next batch's forward fused behind the one-launch update (nullptr: none)
-struct FusedFwd {
-    const dqrm_batch* next;
-    int bits;
-    uint32_t flags;
-    float* out;
-    int64_t ost_t, ost_b;
-};
-
-static int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
-                           int64_t dy_stride_b, int ste, const int64_t* ws_cap_base, int64_t ws_cap_total,
-                           int32_t* ws_rows, float* ws_vals, int32_t* ws_ucount, float* ws_absmax, int grad_bits,
-                           float* s_avg, float lr, int repack_bits, void* workspace, size_t workspace_bytes,
-                           const FusedFwd* ff, void* stream);
 
 int dqrm_emb_bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
                              int64_t dy_stride_t, int64_t dy_stride_b, int ste, const int64_t* ws_cap_base,
@@ -5283,7 +5398,7 @@ int dqrm_emb_bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch,
                              float* ws_absmax, int grad_bits, float* s_avg, float lr, int repack_bits,
                              void* workspace, size_t workspace_bytes, void* stream) {
     return bwd_apply_local(set, batch, dy, dy_stride_t, dy_stride_b, ste, ws_cap_base, ws_cap_total, ws_rows, ws_vals,
-                           ws_ucount, ws_absmax, grad_bits, s_avg, lr, repack_bits, workspace, workspace_bytes, nullptr,
+                           ws_ucount, ws_absmax, grad_bits, s_avg, lr, repack_bits, workspace, workspace_bytes, FusedFwd{},
                            stream);
 }
 
@@ -5294,12 +5409,11 @@ int dqrm_emb_bwd_apply_fwd_local(const dqrm_table_set* set, const dqrm_batch* ba
                                  void* workspace, size_t workspace_bytes, const dqrm_batch* next, int fwd_bits,
                                  uint32_t fwd_flags, float* out, int64_t out_stride_t, int64_t out_stride_b,
                                  void* stream) {
-    FwdArgs fa;  // the forward's arguments, validated as dqrm_emb_fwd validates them
-    int rc = fwd_args(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, "dqrm_emb_bwd_apply_fwd_local", &fa);
+    int rc = check_fwd(set, next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b, "dqrm_emb_bwd_apply_fwd_local");
     if (rc) return rc;
     const FusedFwd ff{next, fwd_bits, fwd_flags, out, out_stride_t, out_stride_b};
     return bwd_apply_local(set, batch, dy, dy_stride_t, dy_stride_b, ste, ws_cap_base, ws_cap_total, ws_rows, ws_vals,
-                           ws_ucount, ws_absmax, grad_bits, s_avg, lr, repack_bits, workspace, workspace_bytes, &ff,
+                           ws_ucount, ws_absmax, grad_bits, s_avg, lr, repack_bits, workspace, workspace_bytes, ff,
                            stream);
 }
 
@@ -5309,7 +5423,7 @@ int dqrm_bwd_apply_fwd_local_is_one_launch(const dqrm_table_set* set, const dqrm
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_bwd_apply_fwd_local_is_one_launch"))) return rc;
     if ((rc = check_batch(next, "dqrm_bwd_apply_fwd_local_is_one_launch"))) return rc;
-    return apply_local_one_launch(set, batch, stream) && fused_fwd_fits(batch, next, fwd_flags) ? 1 : 0;
+    return local_plan(set, batch, next, fwd_flags, stream).fwd_inside ? 1 : 0;
 }
 
 int dqrm_bwd_sgd_fwd_is_one_launch(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
@@ -5318,96 +5432,7 @@ int dqrm_bwd_sgd_fwd_is_one_launch(const dqrm_table_set* set, const dqrm_batch* 
     if (rc) return rc;
     if ((rc = check_batch(batch, "dqrm_bwd_sgd_fwd_is_one_launch"))) return rc;
     if ((rc = check_batch(next, "dqrm_bwd_sgd_fwd_is_one_launch"))) return rc;
-    return sgd_small_plan(set, batch, next, fwd_flags, nullptr) == 2 ? 1 : 0;
-}
-
-}  // extern "C"
-
-int dqrm_internal::emb_check(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next, int bits,
-                             uint32_t fwd_flags, int repack_bits, int training, const char* who) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    if (!(fwd_flags & DQRM_FWD_FULL_PRECISION) && (bits < 2 || bits > 16))
-        return set_error(DQRM_E_INVALID, "%s: embedding_bit %d unsupported", who, bits);
-    if ((fwd_flags & DQRM_FWD_USE_PACKED) && (!set->packed || bits != 4))
-        return set_error(DQRM_E_INVALID, "%s: packed path needs packed rows and bits == 4", who);
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", who, repack_bits);
-    if (!batch) return DQRM_OK;
-    if ((rc = check_batch(batch, who))) return rc;
-    if (next && (rc = check_batch(next, who))) return rc;
-    if (!training) return DQRM_OK;
-    if (bwd_lookup_cap(batch) > 0x3fffffffll)
-        return set_error(DQRM_E_CAPACITY, "%s: max_lookups %lld too large", who, (long long)bwd_lookup_cap(batch));
-    if (set->total_rows > 0xffffffffll) return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 rows", who);
-    return DQRM_OK;
-}
-
-int dqrm_internal::emb_bwd_sgd_launches(const dqrm_table_set* set, const dqrm_batch* batch, const dqrm_batch* next,
-                                        uint32_t fwd_flags) {
-    const int fwd = next && next->num_bags > 0 ? 1 : 0;
-    if (batch->num_bags <= 0) return fwd;
-    const int plan = sgd_small_plan(set, batch, next, fwd_flags, nullptr);
-    if (plan == 2) return 1;
-    if (plan == 1) return 1 + fwd;
-    return 1 + finalize_launch() + fwd;
-}
-
-extern "C" {
-
-static int bwd_apply_local(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
-                           int64_t dy_stride_b, int ste, const int64_t* ws_cap_base, int64_t ws_cap_total,
-                           int32_t* ws_rows, float* ws_vals, int32_t* ws_ucount, float* ws_absmax, int grad_bits,
-                           float* s_avg, float lr, int repack_bits, void* workspace, size_t workspace_bytes,
-                           const FusedFwd* ff, void* stream) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    if ((rc = check_batch(batch, "dqrm_emb_bwd_apply_local"))) return rc;
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", "dqrm_emb_bwd_apply_local");
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || !s_avg || ws_cap_total < 0 ||
-        (((uintptr_t)ws_vals) & 15))
-        return set_error(DQRM_E_INVALID, "%s: null/unaligned workspace", "dqrm_emb_bwd_apply_local");
-    if (grad_bits < 2 || grad_bits > 16)
-        return set_error(DQRM_E_INVALID, "%s: grad_bits must be 2..16 (got %d)", "dqrm_emb_bwd_apply_local", grad_bits);
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)",
-                         "dqrm_emb_bwd_apply_local", repack_bits);
-    if (apply_local_one_launch(set, batch, stream)) {
-        if (batch->num_bags <= 0)  // nothing to update; the next batch's forward still runs
-            return ff ? dqrm_emb_fwd(set, ff->next, ff->bits, ff->flags, ff->out, ff->ost_t, ff->ost_b, stream)
-                      : DQRM_OK;
-        dqrm_internal::CoalesceArgs ca{};
-        ca.meta = set->meta; ca.T = set->num_tables; ca.D = set->dim; ca.B = batch->num_bags; ca.idx = batch->idx;
-        ca.dy = dy; ca.dst_t = dy_stride_t; ca.dst_b = dy_stride_b; ca.scale = set->scale; ca.ste = ste;
-        ca.err = set->err; ca.ws_cap_base = ws_cap_base; ca.ws_rows = ws_rows; ca.ws_vals = ws_vals;
-        ca.ws_ucount = ws_ucount; ca.ws_absmax = ws_absmax;
-        dqrm_internal::LocalApplyArgs la{};
-        la.W = set->W; la.packed = set->packed; la.rowmax = set->rowmax; la.blkmax = set->blkmax;
-        la.sblkmax = set->sblkmax; la.sdirty = set->sdirty; la.bdirty = set->bdirty; la.tmax = set->tmax;
-        la.pscale = set->pscale; la.sync = set->sync; la.s_avg = s_avg; la.bits = grad_bits; la.nlr = -lr;
-        la.repack = repack_bits == 4;
-        dqrm_internal::plan_sub_slots(set->num_rows_host, set->num_tables, &la);
-        const bool fused_fwd = ff && fused_fwd_fits(batch, ff->next, ff->flags);
-        if (fused_fwd) {
-            la.fwd_idx = ff->next->idx; la.fwd_out = ff->out; la.fwd_ost_t = ff->ost_t; la.fwd_ost_b = ff->ost_b;
-            la.fwd_scale = set->scale; la.fwd_bits = ff->bits; la.fwd_flags = ff->flags;
-        }
-        const hipError_t e = dqrm_internal::launch_coalesce_pool1(ca, &la, (hipStream_t)stream);
-        if (e != hipSuccess)
-            return set_error(DQRM_E_HIP, "dqrm_emb_bwd_apply_local: launch failed: %s (%d)", hipGetErrorString(e), (int)e);
-        if (ff && !fused_fwd)
-            return dqrm_emb_fwd(set, ff->next, ff->bits, ff->flags, ff->out, ff->ost_t, ff->ost_b, stream);
-        return DQRM_OK;
-    }
-    if ((rc = dqrm_emb_bwd_coalesce(set, batch, dy, dy_stride_t, dy_stride_b, ste, ws_cap_base, ws_rows, ws_vals,
-                                    ws_ucount, ws_absmax, workspace, workspace_bytes, stream)))
-        return rc;
-    if ((rc = dqrm_apply_local(set, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount, ws_absmax, grad_bits,
-                               s_avg, lr, repack_bits, stream)))
-        return rc;
-    if (ff) return dqrm_emb_fwd(set, ff->next, ff->bits, ff->flags, ff->out, ff->ost_t, ff->ost_b, stream);
-    return DQRM_OK;
+    return sgd_plan(set, batch, next, fwd_flags).fwd_inside ? 1 : 0;
 }
 
 int dqrm_read_errors(const dqrm_table_set* set, uint32_t* flags, int clear, void* stream) {

@@ -410,8 +410,9 @@ int dqrm_apply_sparse_update_strided(const dqrm_table_set* set, const int64_t* c
 /* dqrm_apply_sparse_update_strided on the gathered payloads, then dqrm_emb_fwd(set, next,
  * fwd_bits, fwd_flags, out, out_stride_t, out_stride_b) on the NEXT batch -- the same results as
  * those two calls (W, the |W| hierarchy, scale[] and out bit for bit). When the apply takes the
- * merge kernel (DQRM_APPLY_MERGE / AUTO at 1 < num_ranks <= 16) and `next` is a Criteo-form
- * batch without DQRM_FWD_USE_PACKED, the forward runs in the apply's launch: each table's
+ * merge kernel (only when DQRM_APPLY_MERGE is set, at num_ranks <= 16 and <= 64 tables with the
+ * workspace below; never under AUTO) and `next` is a Criteo-form batch with bags, without
+ * DQRM_FWD_USE_PACKED, the forward runs in the apply's launch: each table's
  * forward workgroups start once that table's update and |W| maxima are final (no finalize or
  * forward launch). When the flat apply kernel takes it (AUTO at num_ranks < dim/4) and the
  * forward reads the exact FP32 rows, the flat kernel's finalize and the forward share ONE launch
