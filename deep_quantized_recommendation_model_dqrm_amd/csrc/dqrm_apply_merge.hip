@@ -104,12 +104,7 @@ DQRM_INLINE void merge_forward(const dqrm_internal::MergeApplyArgs& a, int t, in
             const bool ok = x[k] >= 0 && x[k] < nrows;
             if (!ok && sub == 0) flag_error(a.err, DQRM_ERRF_INDEX);
             float4 y = ok ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!fullp) {
-                y.x = fake_quant(y.x, rr, qlo, qhi) * sv;
-                y.y = fake_quant(y.y, rr, qlo, qhi) * sv;
-                y.z = fake_quant(y.z, rr, qlo, qhi) * sv;
-                y.w = fake_quant(y.w, rr, qlo, qhi) * sv;
-            }
+            if (!fullp) y = fake_quant4_scaled(y, rr, qlo, qhi, sv);
             return y;
         };
         if (wty) {

@@ -32,6 +32,28 @@
 //      segment across chunks).
 // A table's 8 slots run on one XCD (block map below), so dy lines shared by the slices of a
 // dimension-split table come from one L2.
+//
+// The same kernel, k_coalesce_p1, is also the one-launch training step (APPLY, world size 1)
+// and that step with the next batch's forward behind it (FWD). Its stages, in the order they
+// run. Slot geometry, lookups and compaction, order, land + ordered sums and the update are still
+// sections of the kernel's body under a banner of the same name (as functions they moved the
+// kernels' descriptors or the inlining of radix_sort: DESIGN section 8 lists the forms tried);
+// the others are functions defined below the kernel, in this order (prefetch_w,
+// slot_max_and_granule, rendezvous, rereduce_owned_blocks, arrive_and_finalize, next_forward),
+// each with a comment saying what it reads, what it leaves and which LDS is dead after it:
+//   slot geometry            block map, table / slot / sub-slot, rows or dimensions owned
+//   lookups and compaction   1-2 above
+//   order                    3 above; APPLY adds the distinct-rows fast path (no sort)
+//   W prefetch               APPLY: the W rows and block maxima of the slot's entries, and its
+//                            superblock maxima, issued before the land phase
+//   land + ordered sums      4 above; APPLY may keep the coalesced values in the LDS stage
+//   slot max and granule     the slot's max|grad|; APPLY publishes it as an 8-B granule
+//   rendezvous and counts    APPLY: the table's workgroups meet once; the slot counts
+//   update                   APPLY: dqrm_apply_local's arithmetic on the slot's rows
+//   owned-block re-reduction APPLY: blocks whose max holder shrank
+//   arrival, recovery, finalize   APPLY: one arrival per workgroup; the table's last arriver
+//                            applies stalled workgroups' rows and finalizes the table
+//   the next batch's forward FWD: y of the next batch from the updated table
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -77,9 +99,6 @@ constexpr int FIX_MAX = 64;       // largest bucket the MSD pass finishes by ran
 #define DQRM_COAL_CSPAN 4096
 #endif
 constexpr int CSPAN = DQRM_COAL_CSPAN;  // largest row span sorted by counting rows (0: never)
-#ifndef DQRM_COAL_UNIQ
-#define DQRM_COAL_UNIQ 1  // 0: an A/B build without the one-launch step's distinct-rows fast path
-#endif
 constexpr int UNIQ_MAXN = TPB;      // fast path: at most one lookup per thread
 constexpr int UNIQ_HLOG = 12;       // its LDS hash: 4096 slots
 constexpr int UNIQ_HASH = 1 << UNIQ_HLOG;
@@ -436,32 +455,18 @@ __device__ __forceinline__ float chain_sum_rm(const float* c, int p, int pe, int
 // A dimension-split table's workgroup stages its slice (SW = D/8 floats per position) for a
 // few rows with hundreds of lookups each: its cost is the ordered chains, which read 16 B at a
 // time from a dimension-major stage (4 positions per LDS read) but 4 B from a row-major one.
-// DQRM_COAL_DSDM 1: such workgroups take the dimension-major stage under RM too -- in the
+// Such workgroups take the dimension-major stage under RM too (`rmaj` in the kernel) -- in the
 // N > 1 coalesce (APPLY false; TB forced-collectives step 60.4 -> 56.5 us, A/B r5j). In the
 // one-launch step the runtime layout choice cost every table ~1.5 us (38.4 -> 40.7 us/step),
 // so that kernel keeps the compile-time layout.
-#ifndef DQRM_COAL_DSDM
-#define DQRM_COAL_DSDM 1
-#endif
 
 #ifndef DQRM_COAL_WPF
 #define DQRM_COAL_WPF 4
 #endif
-#ifndef DQRM_FWD_EARLY_IDX
-#define DQRM_FWD_EARLY_IDX 0
-#endif
-#ifndef DQRM_COAL_WLATE
-#define DQRM_COAL_WLATE 0  // 1: an A/B build issuing the W prefetch after the land phase
-#endif
-#ifndef DQRM_COAL_CAND
-#define DQRM_COAL_CAND 0  // A/B builds: 1 prefetch candidate blocks' row maxima during the rendezvous,
-#endif                    // 2 the same unless the table already met
 constexpr int WPF = DQRM_COAL_WPF;  // fused update: W float4 per thread loaded during the segment phase
 constexpr int WPFA = WPF > 0 ? WPF : 1;  // array extent (WPF = 0: no early W loads, an A/B build)
 constexpr int OWN_Q = 64;           // fused update: shrunk block-max holders re-reduced in the launch
 constexpr int SBC = 256;            // fused update: superblock maxima of the slot's rows cached in LDS
-constexpr int CAND_SLOTS = 2 * (MAXB * 2) / (BLK * 4);  // row-max caches of candidate blocks (pos + mlist regions)
-static_assert(CAND_SLOTS == 16 && CAND_SLOTS <= NW, "one candidate-block cache per wave");
 constexpr int GRAN_WORD = 32;       // the table's 16 slot granules (8 slots x 2 sub-slots) in its sync words
 static_assert(GRAN_WORD + 2 * SPLIT * 2 <= DQRM_SYNC_STRIDE, "granules fit the table's sync words");
 constexpr uint32_t DIRTY_ONE = 1u << 16;  // arrival counter (sync word 0): arrivals | dirty arrivals << 16
@@ -541,9 +546,8 @@ __device__ __forceinline__ void recover_stalled(const dqrm_internal::CoalesceArg
             const bool ok = x >= 0 && x < nrows;
             const int64_t grow = rb + (ok ? x : 0);
             const float4 w0 = reinterpret_cast<const float4*>(la.W + grow * D)[sub];
-            float4 acc, wn;
-            acc.x = fake_quant(v.x, rr, qlo, qhi) + 0.0f; acc.y = fake_quant(v.y, rr, qlo, qhi) + 0.0f;
-            acc.z = fake_quant(v.z, rr, qlo, qhi) + 0.0f; acc.w = fake_quant(v.w, rr, qlo, qhi) + 0.0f;
+            const float4 acc = fake_quant4_payload(v, rr, qlo, qhi);
+            float4 wn;
             wn.x = upd(w0.x, acc.x); wn.y = upd(w0.y, acc.y); wn.z = upd(w0.z, acc.z); wn.w = upd(w0.w, acc.w);
             if (ok) {  // write-through: a fused forward may read the row from another CU
                 st4_wt(reinterpret_cast<float4*>(la.W + grow * D) + sub, wn);
@@ -588,6 +592,76 @@ __device__ __forceinline__ void recover_stalled(const dqrm_internal::CoalesceArg
     }
 }
 
+// ---- k_coalesce_p1: the state its stage functions take, the kernel, then the stage functions
+// in the order they run (defined below the kernel, so the unit reads top-down) ----
+
+// What this workgroup is and owns; set once in the kernel's slot geometry, const after.
+struct Slot {
+    int t, s, j;     // table, row-range slot, sub-slot
+    int k;           // t * SPLIT + s: the slot's workspace index
+    int kd;          // diagnostic stamp row (sub-slot 1 after all of sub-slot 0)
+    int B;           // lookups per table
+    int K;           // sub-slots of this table's slots
+    int NA, NG;      // the table's active workgroups per sub-slot; its workgroups (granules)
+    int LPR;         // float4 per row
+    bool dsplit;     // dimension-split table
+    int64_t nrows, nblk, r0, r1;  // the table's rows and row blocks; this workgroup's rows [r0, r1)
+    uint64_t* gran;  // the table's granules
+    uint32_t epoch;  // this launch's epoch (lanes of wave 0)
+};
+// The slot's coalesced entries (the ordering stage's U segments) and the table's bases: U from
+// the order, the rest filled by prefetch_w, const after.
+struct Entries {
+    int U;                // distinct rows of this workgroup
+    int ua0, nu0;         // its own row-range slot: first segment, entries
+    int64_t rb, bb, sbb;  // the table's first row, block, superblock
+};
+// What the W prefetch leaves in registers, in flight across the land phase and the rendezvous.
+struct WPrefetch {
+    float4 w[WPFA];   // the W rows of the entries this workgroup updates first (item tid + TPB * i)
+    float blk[WPFA];  // their blocks' maxima
+    float otm;        // the table's max before this step
+    float sbv;        // lane tid < nsbc: a superblock max of the slot's rows (s_sbm after the slot max)
+    int nsbc;         // the slot's superblocks kept in s_sbm (0: the update reads la.sblkmax)
+    int64_t sb0;      // the slot's first superblock
+};
+// Row-range slot sl's entries: segments [ua, ua + nu) (a dimension-split table: its rows in that
+// range; a row split: all U of the workgroup's), entry s_cb[sl] + (u - ua), capped at the region.
+__device__ __forceinline__ void slot_entries(bool dsplit, int U, const int64_t* s_cb, const int* s_uf, int sl, int& ua,
+                                             int& nu) {
+    ua = dsplit ? s_uf[sl] : 0;
+    nu = dsplit ? s_uf[sl + 1] - ua : U;
+    const int cap = (int)(s_cb[sl + 1] - s_cb[sl]);
+    nu = nu < cap ? nu : cap;
+}
+
+template <bool APPLY>
+__device__ __forceinline__ void prefetch_w(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                           const Slot& g, const uint64_t* keys, const uint16_t* hpos, const int64_t* s_cb,
+                                           const int* s_uf, int& s_oq_n, int& s_dirty, Entries& en, WPrefetch& wp);
+template <bool APPLY>
+__device__ __forceinline__ void slot_max_and_granule(const dqrm_internal::CoalesceArgs& a, const Slot& g, const Entries& en,
+                                                     float amax, int nsbc, float sbv, float* s_red, float* s_sbm);
+template <bool APPLY>
+__device__ __forceinline__ void rendezvous(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                           const Slot& g, const Entries& en, const int64_t* s_cb, const int* s_ucnt,
+                                           float& s_am, int& s_stall, int& s_upart);
+__device__ __forceinline__ void rereduce_owned_blocks(const dqrm_internal::LocalApplyArgs& la, const Slot& g, const Entries& en,
+                                                      bool dirty, const uint64_t* keys, const uint16_t* hpos,
+                                                      const float* s_newrm, float* s_blkrm, const int& s_oq_n,
+                                                      const uint32_t* s_oq_blk, const float* s_oq_old,
+                                                      const float* s_oq_sold, int& s_dirty);
+template <bool FWD>
+__device__ __forceinline__ void arrive_and_finalize(const dqrm_internal::CoalesceArgs& a,
+                                                    const dqrm_internal::LocalApplyArgs& la, const Slot& g, const Entries& en,
+                                                    bool go, const uint64_t* keys, const uint16_t* hpos, const int64_t* s_cb,
+                                                    const int& s_upart, const int& s_dirty, int& s_fin, int& s_stallmask,
+                                                    int& s_lastarr, float& s_ftm, int& s_fok, int& s_pub);
+template <int WT>
+__device__ __forceinline__ void next_forward(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                             const Slot& g, const Entries& en, bool go, uint64_t* keys, const int& s_lastarr,
+                                             const int& s_stallmask, const int& s_pub, float& s_ftm, int& s_fok);
+
 // APPLY (dqrm_emb_bwd_apply_local, world size 1): after the coalesce, the table's workgroups
 // meet once (each publishes its max|grad|, then waits for the table's others: all of them are
 // resident, one per CU), and each updates the rows of its row-range slot exactly as
@@ -616,9 +690,7 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     __shared__ float s_am;
     __shared__ int s_stall;
     __shared__ int s_upart;
-    __shared__ uint32_t s_epoch;
     __shared__ float s_sbm[SBC];            // fused update: sblkmax of the slot's superblocks
-    __shared__ int s_cand_blk[CAND_SLOTS];  // fused update: block cached by wave w's row-max slot (-1: none)
     __shared__ int s_oq_n;
     __shared__ int s_dirty;
     __shared__ int s_fin;
@@ -637,6 +709,10 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     int* sdest = reinterpret_cast<int*>(lds + OFF_SDEST);
     float* stage = reinterpret_cast<float*>(lds + OFF_STAGE);
 
+    // ======== slot geometry (the index loads of the next stage go out inside it) ========
+    // reads: blockIdx, the table's uniform values. leaves: t / s / j, r0..r1 or q0 / LG, K, rmaj,
+    // epoch; r[] (index loads) and cbl in flight. Touches no LDS. Two early returns: an idle
+    // spare group, and a dimension slice beyond D.
     // XCD-aware placement: blocks b and b + 8 share an XCD (and its L2), so table t's 8 slots
     // are blocks (t/8)*64 + s*8 + t%8. A dimension-split table's slots read 32-B slices of
     // the same dy lines; on one XCD a line is fetched from HBM once, not once per slot.
@@ -699,7 +775,9 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     const bool active = dsplit ? s < DS : r0 < r1;
     const int SP = (STAGE_FLOATS / SW) & ~3;  // stage entries (dimension-major: the column pitch, 16-B columns)
     const int CE = SP - 4;                    // stage entries per chunk
-    const bool rmaj = RM && !(DQRM_COAL_DSDM && !APPLY && dsplit);
+    // a dimension-split table's workgroups of the N > 1 coalesce: dimension-major under RM too
+    // (measured both ways, "Stage layout" above)
+    const bool rmaj = RM && !(!APPLY && dsplit);
     // stage index of (entry p, dimension d)
     auto sx = [&](int p, int d) -> int { return rmaj ? p * SW + d : d * SP + p; };
     const float* dyt = a.dy + (int64_t)t * a.dst_t;
@@ -710,7 +788,6 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     if (APPLY && tid < WAVE)
         epoch = (gr_epoch(__hip_atomic_load(gran + s + SPLIT * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u) &
                 GR_EPOCH_MASK;
-    if (DQRM_COAL_CAND == 2 && APPLY && tid == 0) s_epoch = epoch;  // (read after the barriers below)
     auto fetch = [&](int b, int sub) -> float4 {
         return reinterpret_cast<const float4*>(dyt + (int64_t)b * a.dst_b)[q0 + sub];
     };
@@ -725,6 +802,15 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
         if (tid == 0) a.ws_absmax[k] = 0.0f;
         return;
     }
+    // fused update: workgroup s updates slots s, s + NA, ... (NA = the table's active workgroups)
+    const int NA = dsplit ? DS : SPLIT;
+    const int NG = NA * K;  // the table's workgroups (granules)
+    const Slot g{t, s, j, k, kd, B, K, NA, NG, LPR, dsplit, nrows, nblk, r0, r1, gran, epoch};
+    // ======== lookups and compaction ========
+    // reads: r[] and cbl (in flight since the geometry). leaves: n, keys[0, n) in lookup order,
+    // kx / krk, the dy prefetch pf in flight, s_cb, s_ucnt = 0, the counting paths' row counters
+    // zeroed (whist in the sort scratch; info at the start of the stage, counted here). Nothing
+    // is dead yet.
     // A dimension-split table combines its slice of EVERY lookup: those dy loads depend on
     // nothing and go out now, in flight with the index loads and across the compaction and
     // sort. A row-split slot issues the same number of placeholder loads (one hot 16-B line,
@@ -804,6 +890,13 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
         }
     }
     CDIAG(2);
+    // ======== order ========
+    // four paths (distinct rows; ranked; atomic; comparison sort + head pass), all leaving the
+    // same: keys sorted (rows ascending, a row's lookups in lookup order), U segments of which M
+    // have several lookups and NS one, and in LDS pos (lookup -> sorted position), hpos (segment
+    // -> first sorted position, hpos[U] = n), mlist (the multi-lookup segments), sdest (sorted
+    // position -> output entry, or -(stage entry) - 1); dimension-split: s_uf, s_ucnt. The sort
+    // scratch, info / minfo and the hash (in the stage) are dead after it.
     uint64_t* tmp = reinterpret_cast<uint64_t*>(lds + OFF_SCR);
     int U, NS, M;
     bool counted = false;
@@ -812,8 +905,11 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     //     slot, nearly always) needs no sort -- every lookup is its own segment, in compaction
     //     (= lookup) order, and the update keeps no order. Distinctness from one LDS hash insert
     //     per lookup. (The N > 1 coalesce keeps the sort: its payload rows must be ascending.)
+    //     Measured: these slots end at 16-18 us instead of 20-22; the step itself did not move
+    //     (the medium and dimension-split tables set its span). Kept because it takes work off
+    //     the wide tables.
     bool uniq = false;
-    if (APPLY && DQRM_COAL_UNIQ && !dsplit && !ranked && !atomic_mode && n <= UNIQ_MAXN) {
+    if (APPLY && !dsplit && !ranked && !atomic_mode && n <= UNIQ_MAXN) {
         uint32_t* hk = reinterpret_cast<uint32_t*>(stage);  // the stage is not used before the land phase
         for (int q = tid; q < UNIQ_HASH; q += TPB) hk[q] = 0u;
         if (tid == 0) s_crowd = 0;
@@ -1096,72 +1192,28 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     }
     }  // comparison sort
     CDIAG(4);
-    // fused update: the entries of row-range slot sl are segments [ua, ua + nu) (a dimension-
-    // split table: its rows in that range; a row split: all of the slot's), entry s_cb[sl] +
-    // (u - ua). Workgroup s updates slots s, s + NA, ... (NA = the table's active workgroups).
-    const int NA = dsplit ? DS : SPLIT;
-    const int NG = NA * K;  // the table's workgroups (granules)
+    // ======== where the slot's entries go (declarations the next three stages share) ========
     const int lpr_sh = __ffs(LPR) - 1;
     // this workgroup's entries in its slot's workspace region: sub-slot 0 (or a whole slot) from
     // its start, sub-slot 1 packed at its end (its values are scratch; its rows are written at
     // their final place, after sub-slot 0's, once the rendezvous has told it sub-slot 0's count)
     auto ebase = [&]() -> int64_t { return j ? s_cb[s + 1] - U : s_cb[s]; };  // (LDS reads, not a live register)
-    auto slot_entries = [&](int sl, int& ua, int& nu) {
-        ua = dsplit ? s_uf[sl] : 0;
-        nu = dsplit ? s_uf[sl + 1] - ua : U;
-        const int cap = (int)(s_cb[sl + 1] - s_cb[sl]);
-        nu = nu < cap ? nu : cap;
-    };
     // a row-split slot whose entries fit beside the stage's multi-lookup values keeps its
     // coalesced values in the stage (entry u, dimension d at column d, index vb0 + u) instead
     // of the workspace: no HBM round trip for them (the workspace values are then not written)
     const int vb0 = n - NS;
     const bool lds_vals = APPLY && !dsplit && vb0 + U <= CE && U <= (int)(s_cb[s + 1] - s_cb[s]);
-    int64_t rb = 0, bb = 0, sbb = 0;
-    int ua0 = 0, nu0 = 0;
-    float4 wpf[WPFA];
-    float bpf[WPFA];
-    float otm = 0.0f;
-    if constexpr (APPLY) {
-        rb = a.meta[t];
-        bb = a.meta[2 * a.T + t];
-        sbb = a.meta[3 * a.T + t];
-        slot_entries(s, ua0, nu0);
-        if (tid == 0) {
-            s_oq_n = 0;
-            s_dirty = 0;
-        }
-        otm = la.tmax[t];
-    }
-    // the W rows and block maxima of the entries this workgroup will update, in flight across
-    // the land and segment phases and the wait for the table's other workgroups: issued before
-    // the land phase (the default; at WPF = 4 both register sets fit the 128-VGPR budget), or
-    // once the dy prefetch registers are free (DQRM_COAL_WLATE=1, an A/B build)
-    auto issue_w = [&]() {
-        if constexpr (APPLY) {
-#pragma unroll
-            for (int jj = 0; jj < WPF; ++jj) {
-                const int q = tid + TPB * jj;
-                wpf[jj] = make_float4(0.f, 0.f, 0.f, 0.f);
-                bpf[jj] = 0.0f;
-                if (q < (nu0 << lpr_sh)) {
-                    const int64_t x = r0 + krow(keys[hpos[ua0 + (q >> lpr_sh)]]);
-                    wpf[jj] = reinterpret_cast<const float4*>(la.W + (rb + x) * a.D)[q & (LPR - 1)];
-                    bpf[jj] = la.blkmax[bb + (x >> 8)];
-                }
-            }
-        }
-    };
-    // the superblock maxima of the slot's rows (a row-split slot spans a few hundred at most),
-    // read by the update's growth / holder checks from LDS instead of a dependent HBM load each.
-    // Read before the update: a stale-low value (another slot's growth) only costs a redundant
-    // atomicMax or superblock re-reduction, never a wrong maximum.
-    const int64_t sb0 = r0 >> 16;
-    const int nsbc = APPLY && !dsplit && r1 > r0 && ((r1 - 1) >> 16) - sb0 < SBC ? (int)(((r1 - 1) >> 16) - sb0 + 1) : 0;
-    float sbv = 0.0f;
-    if (APPLY && tid < nsbc) sbv = la.sblkmax[sbb + sb0 + tid];
-    CDIAG_W(17);  // (diagnostic build: the dy prefetch landed -- before the W rows are issued)
-    if (!DQRM_COAL_WLATE || n - NS > CE) issue_w();
+    // ======== W prefetch: prefetch_w below ========
+    Entries en{U, 0, 0, 0, 0, 0};
+    WPrefetch wp;
+    prefetch_w<APPLY>(a, la, g, keys, hpos, s_cb, s_uf, s_oq_n, s_dirty, en, wp);
+    const int nu0 = en.nu0, nsbc = wp.nsbc;
+    const int64_t rb = en.rb, bb = en.bb, sbb = en.sbb, sb0 = wp.sb0;
+    // ======== land + ordered sums ========
+    // reads: pf (the rest of the dy straight from memory), keys, pos, hpos, mlist, sdest.
+    // leaves: the coalesced rows in ws_vals / ws_rows (or the stage, lds_vals), amax per thread.
+    // dead after it: pf, pos, mlist and sdest (the update reuses sdest for its rows' new maxima);
+    // keys and hpos live on to the arrival, and the key region then holds the forward's lists
     float amax = 0.0f;
     auto emit = [&](int u, int d, float acc) {  // segment u's sum in dimension q0*4 + d
         const int64_t row = r0 + krow(keys[hpos[u]]);
@@ -1233,7 +1285,6 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
             for (int f = 0; f < PF; ++f) store(q + TPB * f, de[f], pf[f]);
             q += TPB * PF;
         }
-        if (DQRM_COAL_WLATE) issue_w();
         for (; q < nitems; q += TPB) {  // beyond the register budget (or no prefetch)
             const int p = pos[q >> lg_sh];
             if (p == 0xFFFF) continue;
@@ -1285,151 +1336,19 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
         }
     }
     CDIAG_W(6);
-    // the workgroup's max|grad| (dimension-split: its slice's) and the slot counts
-    for (int o = WAVE / 2; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, WAVE));
-    if (tid % WAVE == 0) s_red[w] = amax;
-    // a dimension-split table's values are read by its other workgroups: every wave's value
-    // stores land before the granule below signals them (hand-off row 1, sc1 stores)
-    if (APPLY && dsplit) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        float m = 0.0f;
-        for (int q = 0; q < NW; ++q) m = fmaxf(m, s_red[q]);
-        if (K == 1) a.ws_absmax[k] = m;  // sub-slots: sub-slot 0 writes the slot's, after the rendezvous
-        // publish this slot's max|grad| (and distinct rows) as ONE 8-B sc1 store (a data-tagged
-        // granule: no counter, no ordering needed for the value itself)
-        if constexpr (APPLY) {
-            __hip_atomic_store(gran + s + SPLIT * j, gr_make(m, dsplit ? 0 : U, epoch), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            // a slot served alone this launch also advances its sub-slot-1 granule, so both
-            // sub-slots derive the same epoch in a later launch that splits the slot (a parent
-            // set and a one-table view of it plan sub-slots differently; nobody polls it now)
-            if (K == 1 && !dsplit)
-                __hip_atomic_store(gran + s + SPLIT, gr_make(0.0f, 0, epoch), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if constexpr (APPLY) {
-        if (tid < nsbc) s_sbm[tid] = sbv;
-        // While wave 0 waits for the table's other workgroups, every other wave looks for a block
-        // whose row-max holder is one of its (prefetched) rows -- the blocks the update may have
-        // to re-reduce -- and copies the first such block's 256 stored row maxima into its LDS
-        // cache (the pos / mlist regions, dead by now). Rows of a block are updated only by this
-        // workgroup, so the copy stays exact for the untouched rows.
-        if (DQRM_COAL_CAND && !dsplit && w > 0) {
-            int cb = -1;
-            bool met = false;
-            if (DQRM_COAL_CAND == 2) {  // the table already met (this workgroup came last): nothing to hide behind
-                const int l = tid % WAVE;
-                const bool ok = l >= NG || gr_epoch(__hip_atomic_load(gran + l, __ATOMIC_RELAXED,
-                                                                      __HIP_MEMORY_SCOPE_AGENT)) == s_epoch;
-                met = __all(ok);
-            }
-#pragma unroll
-            for (int jj = 0; jj < WPF && !met; ++jj) {
-                const int q = tid + TPB * jj;
-                const bool in = q < (nu0 << lpr_sh);
-                float orm = in ? abs_max4(wpf[jj]) : -1.0f;
-                for (int o = 1; o < LPR; o <<= 1) orm = fmaxf(orm, __shfl_xor(orm, o, WAVE));
-                const bool cand = in && (q & (LPR - 1)) == 0 && orm == bpf[jj];
-                const uint64_t cm = __ballot(cand);
-                if (cb < 0 && cm) {
-                    const int l = __ffsll((unsigned long long)cm) - 1;
-                    const int qq = __builtin_amdgcn_readlane(q, l);
-                    cb = (int)((r0 + krow(keys[hpos[ua0 + (qq >> lpr_sh)]])) >> 8);
-                }
-            }
-            const int lane = tid % WAVE;
-            if (cb >= 0) {
-                float* cache = reinterpret_cast<float*>(w < 8 ? (unsigned char*)pos : (unsigned char*)mlist) + (w & 7) * BLK;
-                float v[BLK / WAVE];
-#pragma unroll
-                for (int i = 0; i < BLK / WAVE; ++i) {
-                    const int64_t r = (int64_t)cb * BLK + lane + i * WAVE;
-                    v[i] = r < nrows ? la.rowmax[rb + r] : 0.0f;
-                }
-#pragma unroll
-                for (int i = 0; i < BLK / WAVE; ++i) cache[lane + i * WAVE] = v[i];
-            }
-            if (lane == 0) s_cand_blk[w] = cb;
-        }
-        if (w == 0 && tid < CAND_SLOTS) {
-            if (tid == 0 || dsplit || !DQRM_COAL_CAND) s_cand_blk[tid] = -1;
-        }
-    }
-    if (APPLY && tid < WAVE) {  // wave 0: lane j polls slot j's granule until it shows this launch's epoch
-        uint64_t g = 0;
-        bool ok = tid >= NG;
-        bool stalled = false;
-        for (int spin = 0;; ++spin) {
-            if (!ok) {
-                g = __hip_atomic_load(gran + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = gr_epoch(g) == epoch;
-            }
-            if (__all(ok)) break;
-            // the table's workgroups were not all resident (the host checks the device's CUs,
-            // the occupancy and the stream's CU mask before it launches this form; another
-            // stream's kernels can still hold CUs): flagged, no hang -- this workgroup does
-            // not update its rows itself (the table scale would come from stale maxima); it
-            // leaves them in the workspace for the table's last-arriving workgroup, which has
-            // every slot's maximum by then (all-or-nothing per table)
-            if (spin > (int)la.spin_limit) {
-                if (tid == 0) flag_error(a.err, DQRM_ERRF_STALL);
-                stalled = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        const float am = wave_max(tid < NG ? __uint_as_float((uint32_t)g) : 0.0f);
-        if (K == 2) {  // the partner sub-slot's count and maximum (uniform: readlane)
-            const int p = j ? s : SPLIT + s;
-            const int upart = __builtin_amdgcn_readlane(gr_count(g), p);
-            const float mself = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)g, s + SPLIT * j));
-            const float mpart = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)g, p));
-            if (tid == 0) {
-                s_upart = upart;
-                if (j == 0 && !stalled) {  // the slot's count and partial maximum, as one workgroup would write them
-                    int c = U + upart;
-                    const int64_t cap = s_cb[s + 1] - s_cb[s];
-                    if (c > cap) {
-                        atomicOr(a.err, DQRM_ERRF_OVERFLOW);
-                        c = (int)cap;
-                    }
-                    a.ws_ucount[k] = c;
-                    a.ws_absmax[k] = fmaxf(mself, mpart);
-                }
-            }
-        }
-        if (tid == 0) {
-            s_am = am;
-            s_stall = stalled ? 1 : 0;
-        }
-    }
-    if (K == 1 && (!dsplit ? tid == 0 : (s == 0 && tid < SPLIT))) {
-        const int sl = dsplit ? tid : s;
-        int c = dsplit ? s_ucnt[sl] : U;
-        const int64_t cap = s_cb[sl + 1] - s_cb[sl];
-        if (c > cap) {
-            atomicOr(a.err, DQRM_ERRF_OVERFLOW);
-            c = (int)cap;
-        }
-        a.ws_ucount[t * SPLIT + sl] = c;
-    }
-    CDIAG_W(7);
+    // ======== the stages behind the land phase, but for the update: functions below ========
+    slot_max_and_granule<APPLY>(a, g, en, amax, nsbc, wp.sbv, s_red, s_sbm);
+    rendezvous<APPLY>(a, la, g, en, s_cb, s_ucnt, s_am, s_stall, s_upart);
     if constexpr (APPLY) {
         __syncthreads();
         CDIAG(11);
-        // (A/B DQRM_FWD_EARLY_IDX=1: the fused forward's next-batch indices issued here, in
-        // flight across the update, instead of after the arrival)
-        int64_t nxe[(FWD && DQRM_FWD_EARLY_IDX) ? MAXI : 1];
-        if constexpr (FWD && DQRM_FWD_EARLY_IDX) {
-#pragma unroll
-            for (int i = 0; i < MAXI; ++i) {
-                const int b = tid + TPB * i;
-                nxe[i] = b < B ? la.fwd_idx[(int64_t)t * B + b] : -1;
-            }
-        }
         CDIAG_W(16);  // (diagnostic build: every load of the workgroup landed, the W prefetch included)
+        // ======== update ========
+        // reads: s_am / s_stall (rendezvous), wpf / bpf / otm, s_sbm, the coalesced values (stage or
+        // workspace), keys, hpos. leaves: W / packed / rowmax of the slot's rows, growth applied,
+        // shrunk block-max holders queued (s_oq_*) or flagged (dirty), s_newrm over sdest; a stalled
+        // workgroup: its entries re-stored. dead after it: the stage's values (rereduce_owned_blocks
+        // takes the region as scratch)
         // the update of dqrm_apply_local: s = clamp(max|g|, 1e-8) / (2^(bits-1)-1) (* 1/N,
         // N = 1), q = clamp(round(g/s)), W += -lr * ((q * 1) * s)
         const float sv = sym_scale(s_am, la.bits) * (float)(1.0 / 1.0);
@@ -1446,18 +1365,14 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
         const bool one_slot = NA == SPLIT;
         // (LDS dead by now: the gather map sdest and the multi-lookup list mlist)
         float* s_newrm = reinterpret_cast<float*>(sdest);  // [nu0]
-        float* s_blkrm = stage;  // [RRW][BLK] per-wave block scratch (the update's values are dead by then)
-        constexpr int RRW = 8;                             // waves re-reducing blocks at a time
-        static_assert(RRW * BLK <= STAGE_FLOATS, "block scratch in the stage region");
+        float* s_blkrm = stage;  // the re-reduction's per-wave block scratch (the update's values are dead by then)
         // item (entry u - ua, float4 sub) of slot sl: w0 = the row's old values, oblk its
         // block's max before this step (a stale-low superblock or table max only costs a
         // redundant atomicMax: within the launch they only grow)
         auto update = [&](int ua, int q, float4 w0, float oblk, float4 v) {
             const int u = ua + (q >> lpr_sh), sub = q & (LPR - 1);
             const int64_t x = r0 + krow(keys[hpos[u]]), grow = rb + x;
-            float4 acc;  // + 0.0f: the payload's integer round trip turns -0 into +0
-            acc.x = fake_quant(v.x, rr, qlo, qhi) + 0.0f; acc.y = fake_quant(v.y, rr, qlo, qhi) + 0.0f;
-            acc.z = fake_quant(v.z, rr, qlo, qhi) + 0.0f; acc.w = fake_quant(v.w, rr, qlo, qhi) + 0.0f;
+            const float4 acc = fake_quant4_payload(v, rr, qlo, qhi);
             float4 wn;
             wn.x = upd(w0.x, acc.x); wn.y = upd(w0.y, acc.y); wn.z = upd(w0.z, acc.z); wn.w = upd(w0.w, acc.w);
             reinterpret_cast<float4*>(la.W + grow * a.D)[sub] = wn;
@@ -1478,7 +1393,7 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
                 atomicMax(reinterpret_cast<unsigned int*>(la.blkmax) + bb + blk, __float_as_uint(rm));
                 if (rm > osb) {
                     atomicMax(reinterpret_cast<unsigned int*>(la.sblkmax) + sb, __float_as_uint(rm));
-                    if (rm > otm) atomicMax(reinterpret_cast<unsigned int*>(la.tmax) + t, __float_as_uint(rm));
+                    if (rm > wp.otm) atomicMax(reinterpret_cast<unsigned int*>(la.tmax) + t, __float_as_uint(rm));
                 }
             }
             if (old_rm == oblk && rm < old_rm) {  // the block's max holder shrank: this slot owns the block
@@ -1535,7 +1450,7 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
         __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt / lgkmcnt not waited
         for (int sl = s, j0 = 0; go && sl < SPLIT; sl += NA, j0 = 1) {  // uniform
             int ua, nu;
-            slot_entries(sl, ua, nu);
+            slot_entries(dsplit, U, s_cb, s_uf, sl, ua, nu);
             const int nit = nu << lpr_sh;
             const float* vb = a.ws_vals + (dsplit ? s_cb[sl] : ebase()) * a.D;  // the entries, D floats each
             int q = tid;
@@ -1555,7 +1470,7 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
                     }
 #pragma unroll
                     for (int j = jh; j < jh + 2 && j < WPF; ++j)
-                        if (q + TPB * j < nit) update(ua, q + TPB * j, wpf[j], bpf[j], v[j - jh]);
+                        if (q + TPB * j < nit) update(ua, q + TPB * j, wp.w[j], wp.blk[j], v[j - jh]);
                 }
                 q += TPB * WPF;
                 CDIAG(14);
@@ -1567,280 +1482,511 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
                 update(ua, q, w0, ob, load_val(vb, q));
             }
         }
-        // owned blocks whose max holder shrank: re-reduce their 256 row maxima
+        // ======== the stages behind the update: functions below ========
+        rereduce_owned_blocks(la, g, en, dirty, keys, hpos, s_newrm, s_blkrm, s_oq_n, s_oq_blk, s_oq_old, s_oq_sold,
+                              s_dirty);
+        arrive_and_finalize<FWD>(a, la, g, en, go, keys, hpos, s_cb, s_upart, s_dirty, s_fin, s_stallmask, s_lastarr,
+                                 s_ftm, s_fok, s_pub);
+        if constexpr (FWD) next_forward<WT>(a, la, g, en, go, keys, s_lastarr, s_stallmask, s_pub, s_ftm, s_fok);
+    }
+}
+
+// Stage: W prefetch (APPLY; the N > 1 coalesce loads nothing: en keeps its zeros, wp.nsbc = 0
+// and wp.w / blk / otm are never read).
+// Reads: en.U, keys and hpos (the order), s_cb, s_uf; the table's bases and old max (a.meta,
+// la.tmax), the W rows and block maxima of the slot's first entries, its superblock maxima.
+// Leaves: en's bases and this workgroup's own entries (ua0, nu0); s_oq_n = s_dirty = 0 for the
+// update (published by the barriers in between); in registers, in flight across the land phase
+// and the rendezvous: wp. Touches no dynamic LDS; the order's scratch, info / minfo and the hash
+// are dead before it.
+template <bool APPLY>
+__device__ __forceinline__ void prefetch_w(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                           const Slot& g, const uint64_t* keys, const uint16_t* hpos, const int64_t* s_cb,
+                                           const int* s_uf, int& s_oq_n, int& s_dirty, Entries& en, WPrefetch& wp) {
+    const int tid = threadIdx.x, t = g.t, kd = g.kd, LPR = g.LPR;
+    (void)kd;
+    const bool dsplit = g.dsplit;
+    const int64_t r0 = g.r0, r1 = g.r1;
+    const int lpr_sh = __ffs(LPR) - 1;
+    if constexpr (APPLY) {
+        en.rb = a.meta[t];
+        en.bb = a.meta[2 * a.T + t];
+        en.sbb = a.meta[3 * a.T + t];
+        slot_entries(dsplit, en.U, s_cb, s_uf, g.s, en.ua0, en.nu0);
+        if (tid == 0) {
+            s_oq_n = 0;
+            s_dirty = 0;
+        }
+        wp.otm = la.tmax[t];
+    }
+    // the W rows and block maxima of the entries this workgroup will update, in flight across
+    // the land and segment phases and the wait for the table's other workgroups: issued before
+    // the land phase. At WPF = 4 both register sets (these and the dy prefetch) fit the 128-VGPR
+    // budget. Issuing them only once the dy prefetch registers were free (after the land phase's
+    // first round) looked good in phase clocks and cost ~0.5 us per step in the A/B (DESIGN
+    // section 8)
+    auto issue_w = [&]() {
+        if constexpr (APPLY) {
+#pragma unroll
+            for (int jj = 0; jj < WPF; ++jj) {
+                const int q = tid + TPB * jj;
+                wp.w[jj] = make_float4(0.f, 0.f, 0.f, 0.f);
+                wp.blk[jj] = 0.0f;
+                if (q < (en.nu0 << lpr_sh)) {
+                    const int64_t x = r0 + krow(keys[hpos[en.ua0 + (q >> lpr_sh)]]);
+                    wp.w[jj] = reinterpret_cast<const float4*>(la.W + (en.rb + x) * a.D)[q & (LPR - 1)];
+                    wp.blk[jj] = la.blkmax[en.bb + (x >> 8)];
+                }
+            }
+        }
+    };
+    // the superblock maxima of the slot's rows (a row-split slot spans a few hundred at most),
+    // read by the update's growth / holder checks from LDS instead of a dependent HBM load each.
+    // Read before the update: a stale-low value (another slot's growth) only costs a redundant
+    // atomicMax or superblock re-reduction, never a wrong maximum.
+    wp.sb0 = r0 >> 16;
+    wp.nsbc = APPLY && !dsplit && r1 > r0 && ((r1 - 1) >> 16) - wp.sb0 < SBC ? (int)(((r1 - 1) >> 16) - wp.sb0 + 1) : 0;
+    wp.sbv = 0.0f;
+    if (APPLY && tid < wp.nsbc) wp.sbv = la.sblkmax[en.sbb + wp.sb0 + tid];
+    CDIAG_W(17);  // (diagnostic build: the dy prefetch landed -- before the W rows are issued)
+    issue_w();
+}
+
+// Stage: slot max and granule.
+// Reads: every thread's amax (the land phase); APPLY: the slot's superblock maxima the W
+// prefetch loaded (lane tid < nsbc holds sbv).
+// Leaves: ws_absmax[k] (K == 1); APPLY: this slot's granule {max|grad|, distinct rows, epoch}
+// published to the table's other workgroups -- a dimension-split table's only after every
+// wave's value stores have landed, since those workgroups read them -- and s_sbm (the update).
+// LDS: s_red is scratch; pos is dead from here on (the land phase was its last reader).
+template <bool APPLY>
+__device__ __forceinline__ void slot_max_and_granule(const dqrm_internal::CoalesceArgs& a, const Slot& g, const Entries& en,
+                                                     float amax, int nsbc, float sbv, float* s_red, float* s_sbm) {
+    const int tid = threadIdx.x, w = tid / WAVE, s = g.s, j = g.j, k = g.k, K = g.K, U = en.U;
+    const bool dsplit = g.dsplit;
+    uint64_t* gran = g.gran;
+    const uint32_t epoch = g.epoch;
+    // the workgroup's max|grad| (dimension-split: its slice's) and the slot counts
+    for (int o = WAVE / 2; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, WAVE));
+    if (tid % WAVE == 0) s_red[w] = amax;
+    // a dimension-split table's values are read by its other workgroups: every wave's value
+    // stores land before the granule below signals them (hand-off row 1, sc1 stores)
+    if (APPLY && dsplit) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        float m = 0.0f;
+        for (int q = 0; q < NW; ++q) m = fmaxf(m, s_red[q]);
+        if (K == 1) a.ws_absmax[k] = m;  // sub-slots: sub-slot 0 writes the slot's, after the rendezvous
+        // publish this slot's max|grad| (and distinct rows) as ONE 8-B sc1 store (a data-tagged
+        // granule: no counter, no ordering needed for the value itself)
+        if constexpr (APPLY) {
+            __hip_atomic_store(gran + s + SPLIT * j, gr_make(m, dsplit ? 0 : U, epoch), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            // a slot served alone this launch also advances its sub-slot-1 granule, so both
+            // sub-slots derive the same epoch in a later launch that splits the slot (a parent
+            // set and a one-table view of it plan sub-slots differently; nobody polls it now)
+            if (K == 1 && !dsplit)
+                __hip_atomic_store(gran + s + SPLIT, gr_make(0.0f, 0, epoch), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if constexpr (APPLY) {
+        if (tid < nsbc) s_sbm[tid] = sbv;
+    }
+}
+
+// Stage: rendezvous and counts.
+// Reads: the table's granules (APPLY), s_ucnt (dimension-split), s_cb.
+// Leaves: APPLY: s_am = the table's max|grad|, s_stall = this workgroup gave up waiting,
+// s_upart = the partner sub-slot's distinct rows (K == 2), all three published by the barrier
+// that opens the update; ws_ucount of the slot (K == 2: with ws_absmax, by sub-slot 0).
+// LDS: touches none of the dynamic regions.
+template <bool APPLY>
+__device__ __forceinline__ void rendezvous(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                           const Slot& g, const Entries& en, const int64_t* s_cb, const int* s_ucnt,
+                                           float& s_am, int& s_stall, int& s_upart) {
+    const int tid = threadIdx.x, t = g.t, s = g.s, j = g.j, k = g.k, kd = g.kd, K = g.K, NG = g.NG, U = en.U;
+    (void)kd;
+    const bool dsplit = g.dsplit;
+    const uint64_t* gran = g.gran;
+    const uint32_t epoch = g.epoch;
+    if (APPLY && tid < WAVE) {  // wave 0: lane j polls slot j's granule until it shows this launch's epoch
+        uint64_t gv = 0;
+        bool ok = tid >= NG;
+        bool stalled = false;
+        for (int spin = 0;; ++spin) {
+            if (!ok) {
+                gv = __hip_atomic_load(gran + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok = gr_epoch(gv) == epoch;
+            }
+            if (__all(ok)) break;
+            // the table's workgroups were not all resident (the host checks the device's CUs,
+            // the occupancy and the stream's CU mask before it launches this form; another
+            // stream's kernels can still hold CUs): flagged, no hang -- this workgroup does
+            // not update its rows itself (the table scale would come from stale maxima); it
+            // leaves them in the workspace for the table's last-arriving workgroup, which has
+            // every slot's maximum by then (all-or-nothing per table)
+            if (spin > (int)la.spin_limit) {
+                if (tid == 0) flag_error(a.err, DQRM_ERRF_STALL);
+                stalled = true;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        const float am = wave_max(tid < NG ? __uint_as_float((uint32_t)gv) : 0.0f);
+        if (K == 2) {  // the partner sub-slot's count and maximum (uniform: readlane)
+            const int p = j ? s : SPLIT + s;
+            const int upart = __builtin_amdgcn_readlane(gr_count(gv), p);
+            const float mself = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)gv, s + SPLIT * j));
+            const float mpart = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)gv, p));
+            if (tid == 0) {
+                s_upart = upart;
+                if (j == 0 && !stalled) {  // the slot's count and partial maximum, as one workgroup would write them
+                    int c = U + upart;
+                    const int64_t cap = s_cb[s + 1] - s_cb[s];
+                    if (c > cap) {
+                        atomicOr(a.err, DQRM_ERRF_OVERFLOW);
+                        c = (int)cap;
+                    }
+                    a.ws_ucount[k] = c;
+                    a.ws_absmax[k] = fmaxf(mself, mpart);
+                }
+            }
+        }
+        if (tid == 0) {
+            s_am = am;
+            s_stall = stalled ? 1 : 0;
+        }
+    }
+    if (K == 1 && (!dsplit ? tid == 0 : (s == 0 && tid < SPLIT))) {
+        const int sl = dsplit ? tid : s;
+        int c = dsplit ? s_ucnt[sl] : U;
+        const int64_t cap = s_cb[sl + 1] - s_cb[sl];
+        if (c > cap) {
+            atomicOr(a.err, DQRM_ERRF_OVERFLOW);
+            c = (int)cap;
+        }
+        a.ws_ucount[t * SPLIT + sl] = c;
+    }
+    CDIAG_W(7);
+}
+
+// Stage: owned-block re-reduction (APPLY). Opens with the barrier behind the update.
+// Reads: the queue s_oq_n / s_oq_blk / s_oq_old / s_oq_sold the update filled; `dirty`, whether
+// the update flagged a block itself; for a workgroup of one row-range slot its rows' new maxima
+// s_newrm[nu0] (the update left them over sdest) with keys / hpos.
+// Leaves: blkmax of every queued block exact, the superblocks those held flagged (sdirty), and
+// s_dirty = this workgroup flagged something (read by arrive_and_finalize).
+// LDS: s_blkrm, [RRW][BLK] floats at the start of the stage region, is scratch (the update's
+// values there are dead); pos and mlist stay dead.
+__device__ __forceinline__ void rereduce_owned_blocks(const dqrm_internal::LocalApplyArgs& la, const Slot& g, const Entries& en,
+                                                      bool dirty, const uint64_t* keys, const uint16_t* hpos,
+                                                      const float* s_newrm, float* s_blkrm, const int& s_oq_n,
+                                                      const uint32_t* s_oq_blk, const float* s_oq_old,
+                                                      const float* s_oq_sold, int& s_dirty) {
+    const int tid = threadIdx.x, w = tid / WAVE, kd = g.kd, ua0 = en.ua0, nu0 = en.nu0;
+    (void)kd;
+    const int64_t nrows = g.nrows, r0 = g.r0, rb = en.rb, bb = en.bb, sbb = en.sbb;
+    const bool one_slot = g.NA == SPLIT;
+    constexpr int RRW = 8;  // waves re-reducing blocks at a time
+    static_assert(RRW * BLK <= STAGE_FLOATS, "block scratch in the stage region");
+    // owned blocks whose max holder shrank: re-reduce their 256 row maxima
+    __syncthreads();
+    CDIAG(15);
+    const int nq = s_oq_n < OWN_Q ? s_oq_n : OWN_Q;
+    if (nq > 0 && !one_slot) {  // uniform: the stored maxima (write-through), once they have landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        CDIAG(15);
-        const int nq = s_oq_n < OWN_Q ? s_oq_n : OWN_Q;
-        if (nq > 0 && !one_slot) {  // uniform: the stored maxima (write-through), once they have landed
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        const int lane = tid % WAVE;
-        for (int qi = w; qi < nq && (w < RRW || !one_slot); qi += one_slot ? RRW : NW) {  // one wave per block
-            const int64_t blk = s_oq_blk[qi];
-            float mv = 0.0f;
-            if (one_slot) {
-                // the block's untouched rows keep their stored maxima; its touched rows (the
-                // slot's entries [e0, e1), ascending rows) take their new maxima from LDS
-                float* sc = s_blkrm + w * BLK;
-                int ci = -1;  // a wave's cache holds this block's stored row maxima already
-                for (int c = 1; c < CAND_SLOTS; ++c)
-                    if (ci < 0 && s_cand_blk[c] == (int)blk) ci = c;
-                if (ci >= 0) {
-                    sc = reinterpret_cast<float*>(ci < 8 ? (unsigned char*)pos : (unsigned char*)mlist) + (ci & 7) * BLK;
-                } else {
+    }
+    const int lane = tid % WAVE;
+    for (int qi = w; qi < nq && (w < RRW || !one_slot); qi += one_slot ? RRW : NW) {  // one wave per block
+        const int64_t blk = s_oq_blk[qi];
+        float mv = 0.0f;
+        if (one_slot) {
+            // the block's untouched rows keep their stored maxima; its touched rows (the
+            // slot's entries [e0, e1), ascending rows) take their new maxima from LDS
+            float* sc = s_blkrm + w * BLK;
 #pragma unroll
-                    for (int i = 0; i < BLK / WAVE; ++i) {
-                        const int64_t r = blk * BLK + lane + i * WAVE;
-                        sc[lane + i * WAVE] = r < nrows ? la.rowmax[rb + r] : 0.0f;
-                    }
+            for (int i = 0; i < BLK / WAVE; ++i) {
+                const int64_t r = blk * BLK + lane + i * WAVE;
+                sc[lane + i * WAVE] = r < nrows ? la.rowmax[rb + r] : 0.0f;
+            }
+            if (nu0 <= 16 * WAVE) {  // every lane tests its entries (independent LDS reads, no search)
+                for (int e = lane; e < nu0; e += WAVE) {
+                    const int64_t x = r0 + krow(keys[hpos[ua0 + e]]);
+                    if ((x >> 8) == blk) sc[x & (BLK - 1)] = s_newrm[e];
                 }
-                if (nu0 <= 16 * WAVE) {  // every lane tests its entries (independent LDS reads, no search)
-                    for (int e = lane; e < nu0; e += WAVE) {
-                        const int64_t x = r0 + krow(keys[hpos[ua0 + e]]);
-                        if ((x >> 8) == blk) sc[x & (BLK - 1)] = s_newrm[e];
-                    }
-                } else {
-                    auto first_at_least = [&](int64_t row) {  // first entry with a row >= `row`
-                        int lo = 0, hi = nu0;
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (r0 + (int64_t)krow(keys[hpos[ua0 + mid]]) < row) lo = mid + 1; else hi = mid;
-                        }
-                        return lo;
-                    };
-                    const int e0 = first_at_least(blk * BLK), e1 = first_at_least((blk + 1) * BLK);
-                    for (int e = e0 + lane; e < e1; e += WAVE)
-                        sc[(r0 + krow(keys[hpos[ua0 + e]])) & (BLK - 1)] = s_newrm[e];
-                }
-#pragma unroll
-                for (int i = 0; i < BLK / WAVE; ++i) mv = fmaxf(mv, sc[lane + i * WAVE]);
             } else {
+                auto first_at_least = [&](int64_t row) {  // first entry with a row >= `row`
+                    int lo = 0, hi = nu0;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (r0 + (int64_t)krow(keys[hpos[ua0 + mid]]) < row) lo = mid + 1; else hi = mid;
+                    }
+                    return lo;
+                };
+                const int e0 = first_at_least(blk * BLK), e1 = first_at_least((blk + 1) * BLK);
+                for (int e = e0 + lane; e < e1; e += WAVE)
+                    sc[(r0 + krow(keys[hpos[ua0 + e]])) & (BLK - 1)] = s_newrm[e];
+            }
 #pragma unroll
-                for (int i = 0; i < BLK / WAVE; ++i) {
-                    const int64_t r = blk * BLK + lane + i * WAVE;
-                    if (r < nrows) mv = fmaxf(mv, ld_wt(la.rowmax + rb + r));
-                }
-            }
-            mv = wave_max(mv);
-            if (lane == 0) {
-                st_wt(la.blkmax + bb + blk, mv);
-                // it held the superblock's max before this step: the finalize re-reduces the
-                // superblock (exact whatever grew meanwhile)
-                if (mv < s_oq_old[qi] && s_oq_old[qi] == s_oq_sold[qi]) {
-                    flag_set(la.sdirty, sbb + (blk >> 8));
-                    dirty = true;
-                }
+            for (int i = 0; i < BLK / WAVE; ++i) mv = fmaxf(mv, sc[lane + i * WAVE]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < BLK / WAVE; ++i) {
+                const int64_t r = blk * BLK + lane + i * WAVE;
+                if (r < nrows) mv = fmaxf(mv, ld_wt(la.rowmax + rb + r));
             }
         }
-        if (dirty) s_dirty = 1;
-        if (j == 1 && go) {  // sub-slot 1's rows, at their place after sub-slot 0's entries (stalled: left for the recovery)
-            const int nr = U < (int)(s_cb[s + 1] - s_cb[s]) - s_upart ? U : (int)(s_cb[s + 1] - s_cb[s]) - s_upart;
-            for (int u = tid; u < nr; u += TPB) a.ws_rows[s_cb[s] + s_upart + u] = (int32_t)(r0 + krow(keys[hpos[u]]));
+        mv = wave_max(mv);
+        if (lane == 0) {
+            st_wt(la.blkmax + bb + blk, mv);
+            // it held the superblock's max before this step: the finalize re-reduces the
+            // superblock (exact whatever grew meanwhile)
+            if (mv < s_oq_old[qi] && s_oq_old[qi] == s_oq_sold[qi]) {
+                flag_set(la.sdirty, sbb + (blk >> 8));
+                dirty = true;
+            }
         }
-        CDIAG(12);
-        // one arrival per workgroup after all its stores landed, carrying whether it flagged
-        // a superblock (hand-off row 1 of MI355X_MICROARCH.md: sc1 stores / atomics, vmcnt(0),
-        // barrier, one lane's agent-scope add; the last arriver reads with sc1 loads only).
-        // The last one re-reduces the flagged superblocks and the table max -- only if some
-        // workgroup flagged one -- and re-arms the counter.
+    }
+    if (dirty) s_dirty = 1;
+}
+
+// Stage: arrival, recovery, finalize (APPLY).
+// Reads: s_dirty (rereduce_owned_blocks), s_upart (rendezvous), go (false: this workgroup
+// stalled at the rendezvous), keys / hpos, s_cb.
+// Leaves: sub-slot 1's rows in ws_rows behind sub-slot 0's; the workgroup's one arrival at the
+// table's counter, after all its stores landed; in the table's last arriver the stalled
+// workgroups' rows applied (recover_stalled) and the table finalized if anything was flagged;
+// s_lastarr, s_stallmask, s_fin, s_pub, and -- FWD, nothing to finalize -- the table's final max
+// published at once with s_ftm / s_fok. next_forward reads all six.
+// LDS: touches none of the dynamic regions; keys and hpos are dead after it.
+template <bool FWD>
+__device__ __forceinline__ void arrive_and_finalize(const dqrm_internal::CoalesceArgs& a,
+                                                    const dqrm_internal::LocalApplyArgs& la, const Slot& g, const Entries& en,
+                                                    bool go, const uint64_t* keys, const uint16_t* hpos, const int64_t* s_cb,
+                                                    const int& s_upart, const int& s_dirty, int& s_fin, int& s_stallmask,
+                                                    int& s_lastarr, float& s_ftm, int& s_fok, int& s_pub) {
+    const int tid = threadIdx.x, t = g.t, s = g.s, j = g.j, kd = g.kd, K = g.K, NA = g.NA, NG = g.NG, U = en.U;
+    (void)kd;
+    const bool dsplit = g.dsplit;
+    const int64_t nblk = g.nblk, r0 = g.r0;
+    const uint64_t* gran = g.gran;
+    const uint32_t epoch = g.epoch;
+    if (j == 1 && go) {  // sub-slot 1's rows, at their place after sub-slot 0's entries (stalled: left for the recovery)
+        const int nr = U < (int)(s_cb[s + 1] - s_cb[s]) - s_upart ? U : (int)(s_cb[s + 1] - s_cb[s]) - s_upart;
+        for (int u = tid; u < nr; u += TPB) a.ws_rows[s_cb[s] + s_upart + u] = (int32_t)(r0 + krow(keys[hpos[u]]));
+    }
+    CDIAG(12);
+    // one arrival per workgroup after all its stores landed, carrying whether it flagged
+    // a superblock (hand-off row 1 of MI355X_MICROARCH.md: sc1 stores / atomics, vmcnt(0),
+    // barrier, one lane's agent-scope add; the last arriver reads with sc1 loads only).
+    // The last one re-reduces the flagged superblocks and the table max -- only if some
+    // workgroup flagged one -- and re-arms the counter.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t* cnt = la.sync + (int64_t)t * DQRM_SYNC_STRIDE;
+        const uint32_t add = 1u + (s_dirty ? DIRTY_ONE : 0u);
+        const uint32_t now = atomicAdd(cnt, add) + add;
+        const bool last = (now & (DIRTY_ONE - 1u)) == (uint32_t)NG;
+        uint32_t sm = 0u;
+        if (last) {
+            __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sm = ld_wt(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD);
+            if (sm) __hip_atomic_store(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD, 0u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        }
+        s_stallmask = (int)sm;
+        s_lastarr = last ? 1 : 0;
+        s_fin = last && ((now >> 16) != 0u || sm != 0u);
+        s_pub = 0;
+        if (FWD && last && !s_fin) {
+            // fused forward: nothing to finalize or recover, so the table max is final now
+            // (every workgroup's growth atomics landed before its arrival): published at
+            // once, the table's other workgroups wait on it (step 9)
+            const float tm = ld_wt(la.tmax + t);
+            s_ftm = tm;
+            s_fok = 1;
+            s_pub = 1;
+            __hip_atomic_store(reinterpret_cast<uint64_t*>(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + FWD_WORD),
+                               gr_make(tm, 0, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (s_stallmask) {  // uniform, rare: apply the stalled workgroups' rows (then finalize)
+        recover_stalled(a, la, t, (uint32_t)s_stallmask, gran, NG, K, dsplit, NA, nblk, s_cb);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    if (s_fin)
+        finalize_table<true>(make_meta(a.meta, a.T), t, la.W, la.rowmax, la.blkmax, la.sblkmax, la.sdirty,
+                             la.bdirty, la.tmax, a.D, true, false);
+    CDIAG_W(13);
+}
+
+// Stage: the NEXT batch's forward (FWD; dqrm_emb_bwd_apply_fwd_local): emb_fwd_table's
+// arithmetic for pooling 1, y[b] = fake-quant(W[row_b]) with the scale of the updated
+// table. The table's last arriver publishes its final max (FWD_WORD granule, after
+// the finalize); the others wait for it. Which workgroup gathers which lookup: a row
+// split the rows of its own range -- updated by itself (or untouched) -- so its row
+// loads go out before the wait; a dimension-split table (one XCD, no sub-slots) deals
+// the lookups round-robin and reads after the wait, from the XCD's L2. Out-of-range
+// rows: workgroup (0, 0) writes zeros and flags them. A stalled workgroup's share (its
+// rows were applied by the last arriver) is the last arriver's.
+// Reads: arrive_and_finalize's s_lastarr / s_stallmask / s_pub (and s_ftm / s_fok where it
+// published them; otherwise this stage sets both), go.
+// Leaves: fwd_out, and fwd_scale under DQRM_FWD_REFRESH_SCALE.
+// LDS: the key region, dead since the arrival, holds the per-wave lookup lists.
+template <int WT>
+__device__ __forceinline__ void next_forward(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                             const Slot& g, const Entries& en, bool go, uint64_t* keys, const int& s_lastarr,
+                                             const int& s_stallmask, const int& s_pub, float& s_ftm, int& s_fok) {
+    const int tid = threadIdx.x, w = tid / WAVE, t = g.t, s = g.s, j = g.j, kd = g.kd, B = g.B, K = g.K, NA = g.NA;
+    (void)kd;
+    const int LPR = g.LPR;
+    const bool dsplit = g.dsplit;
+    const int64_t nrows = g.nrows, nblk = g.nblk, rb = en.rb;
+    const uint32_t epoch = g.epoch;
+    const bool refresh = (la.fwd_flags & DQRM_FWD_REFRESH_SCALE) != 0;
+    const bool fullp = (la.fwd_flags & DQRM_FWD_FULL_PRECISION) != 0;
+    uint64_t* fword = reinterpret_cast<uint64_t*>(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + FWD_WORD);
+    if (s_lastarr && !s_pub) {  // after the recovery / finalize: the final max, then published
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) {
-            uint32_t* cnt = la.sync + (int64_t)t * DQRM_SYNC_STRIDE;
-            const uint32_t add = 1u + (s_dirty ? DIRTY_ONE : 0u);
-            const uint32_t now = atomicAdd(cnt, add) + add;
-            const bool last = (now & (DIRTY_ONE - 1u)) == (uint32_t)NG;
-            uint32_t sm = 0u;
-            if (last) {
-                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                sm = ld_wt(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD);
-                if (sm) __hip_atomic_store(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD, 0u, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-            }
-            s_stallmask = (int)sm;
-            s_lastarr = last ? 1 : 0;
-            s_fin = last && ((now >> 16) != 0u || sm != 0u);
-            s_pub = 0;
-            if (FWD && last && !s_fin) {
-                // fused forward: nothing to finalize or recover, so the table max is final now
-                // (every workgroup's growth atomics landed before its arrival): published at
-                // once, the table's other workgroups wait on it (step 9)
-                const float tm = ld_wt(la.tmax + t);
-                s_ftm = tm;
-                s_fok = 1;
-                s_pub = 1;
-                __hip_atomic_store(reinterpret_cast<uint64_t*>(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + FWD_WORD),
-                                   gr_make(tm, 0, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        __syncthreads();
-        if (s_stallmask) {  // uniform, rare: apply the stalled workgroups' rows (then finalize)
-            recover_stalled(a, la, t, (uint32_t)s_stallmask, gran, NG, K, dsplit, NA, nblk, s_cb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        if (s_fin)
-            finalize_table<true>(make_meta(a.meta, a.T), t, la.W, la.rowmax, la.blkmax, la.sblkmax, la.sdirty,
-                                 la.bdirty, la.tmax, a.D, true, false);
-        CDIAG_W(13);
-        // 9. the NEXT batch's forward (dqrm_emb_bwd_apply_fwd_local): emb_fwd_table's
-        //    arithmetic for pooling 1, y[b] = fake-quant(W[row_b]) with the scale of the updated
-        //    table. The table's last arriver publishes its final max (FWD_WORD granule, after
-        //    the finalize); the others wait for it. Which workgroup gathers which lookup: a row
-        //    split the rows of its own range -- updated by itself (or untouched) -- so its row
-        //    loads go out before the wait; a dimension-split table (one XCD, no sub-slots) deals
-        //    the lookups round-robin and reads after the wait, from the XCD's L2. Out-of-range
-        //    rows: workgroup (0, 0) writes zeros and flags them. A stalled workgroup's share (its
-        //    rows were applied by the last arriver) is the last arriver's.
-        if constexpr (FWD) {
-            const bool refresh = (la.fwd_flags & DQRM_FWD_REFRESH_SCALE) != 0;
-            const bool fullp = (la.fwd_flags & DQRM_FWD_FULL_PRECISION) != 0;
-            uint64_t* fword = reinterpret_cast<uint64_t*>(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + FWD_WORD);
-            if (s_lastarr && !s_pub) {  // after the recovery / finalize: the final max, then published
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0) {
-                    const float tm = ld_wt(la.tmax + t);
-                    s_ftm = tm;
-                    s_fok = 1;
-                    __hip_atomic_store(fword, gr_make(tm, 0, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            // (i) this workgroup's lookups of the next batch -- they do not depend on the table's
-            //     final max -- as per-wave LDS lists {row | 0xFFFFFFFF, b} in lookup order (the
-            //     key region is dead by now). A dimension-split table deals its lookups round-robin
-            //     over its NA workgroups (every wave gets some); a row split takes the rows of its
-            //     own range; the last arriver also the stalled workgroups' shares.
-            int64_t nx[MAXI];
-#pragma unroll
-            for (int i = 0; i < MAXI; ++i) {
-                const int b = tid + TPB * i;
-                if constexpr (DQRM_FWD_EARLY_IDX) nx[i] = nxe[i];
-                else nx[i] = b < B ? la.fwd_idx[(int64_t)t * B + b] : -1;
-            }
-            const int me = s + SPLIT * j;
-            const uint32_t smask = s_lastarr ? (uint32_t)s_stallmask : 0u;
-            const int lane = tid % WAVE;
-            uint64_t* lst = keys + w * (WAVE * MAXI);
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < MAXI; ++i) {
-                const int b = tid + TPB * i;
-                const int64_t x = nx[i];
-                const bool okr = x >= 0 && x < nrows;
-                int own = 0;
-                if (dsplit) {
-                    own = b % NA;
-                } else if (okr) {
-                    const int sl = slot_of_row(x, nblk);
-                    int jj = 0;
-                    if (K == 2) {
-                        const int64_t b0 = nblk * sl / SPLIT, b1 = nblk * (sl + 1) / SPLIT;
-                        jj = (x >> 8) >= (b0 + b1) / 2 ? 1 : 0;
-                    }
-                    own = sl + SPLIT * jj;
-                }
-                const bool mine = b < B && ((own == me && go) || ((smask >> own) & 1u));
-                const uint64_t m = __ballot(mine);
-                if (mine) {
-                    const int p = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    lst[p] = ((uint64_t)(okr ? (uint32_t)x : 0xFFFFFFFFu) << 32) | (uint32_t)b;
-                    if (!okr) flag_error(a.err, DQRM_ERRF_INDEX);
-                }
-                cnt += __popcll(m);
-            }
-            CDIAG(20);
-            // (ii) a row split reads only rows it updated itself (or untouched ones): its first
-            //      rows go out now, in flight across the wait for the table's final max. Plain
-            //      loads: a workgroup's own stores are visible to it, and a dimension-split
-            //      table's rows (other workgroups' stores, one XCD) were never loaded by this CU
-            //      in this launch -- its slot ranges are block-aligned, no line is shared -- so
-            //      they come from the XCD's L2, once the wait below has ordered them.
-            const int G = LPR < WAVE ? WAVE / LPR : 1;  // rows per wave pass
-            const int gl = lane / LPR, sub = lane % LPR;
-            constexpr int FU = 4;  // rows per lane group in flight
-            uint64_t e[FU];
-            float4 v[FU];
-            auto issue = [&](int p0) {
-#pragma unroll
-                for (int u = 0; u < FU; ++u) {
-                    const int ix = p0 + gl + G * u;
-                    e[u] = ix < cnt && lane < G * LPR ? lst[ix] : ~0ull;
-                }
-#pragma unroll
-                for (int u = 0; u < FU; ++u) {
-                    const uint32_t x = (uint32_t)(e[u] >> 32);
-                    v[u] = nrows > 0 ? reinterpret_cast<const float4*>(la.W + (rb + (x != 0xFFFFFFFFu ? x : 0u)) * a.D)[sub]
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            };
-            if (!dsplit && cnt > 0) issue(0);
-            // (iii) the table's final max: published by the last arriver (above, or at its
-            //       arrival), the others wait for it
-            if (!s_lastarr && tid == 0) {
-                // a workgroup that stalled at the rendezvous leaves its share to the last arriver
-                // and does not wait (its CU may be what a late workgroup of the table needs);
-                // the others met every workgroup of the table there, so all of them arrive
-                uint64_t g = 0;
-                int ok = go ? 1 : 0;
-                for (uint32_t spin = 0; ok; ++spin) {
-                    g = __hip_atomic_load(fword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (gr_epoch(g) == epoch) break;
-                    if (spin > (1u << 20)) {  // (never, all resident) flagged, this share skipped
-                        flag_error(a.err, DQRM_ERRF_STALL);
-                        ok = 0;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                s_ftm = __uint_as_float((uint32_t)g);
-                s_fok = ok;
-            }
-            __syncthreads();
-            CDIAG(19);
-            if (!s_fok) cnt = 0;  // (uniform)
-            const float sf = fullp ? 1.0f : (refresh ? sym_scale(s_ftm, la.fwd_bits) : la.fwd_scale[t]);
-            if (refresh && !fullp && s_lastarr && tid == 0) la.fwd_scale[t] = sf;
-            const float rf = 1.0f / sf;
-            const float fqlo = -(float)(1 << (la.fwd_bits - 1)), fqhi = (float)((1 << (la.fwd_bits - 1)) - 1);
-            float* outt = la.fwd_out + (int64_t)t * la.fwd_ost_t;
-            constexpr bool wty = (WT & WT_Y) != 0;
-            for (int p0 = 0; p0 < cnt; p0 += G * FU) {  // uniform per wave
-                if (p0 > 0 || dsplit) issue(p0);  // (the first rows of a row split went out before the wait)
-                if (p0 == 0) CDIAG_W(21);
-                auto quant = [&](int u) -> float4 {
-                    float4 y = (uint32_t)(e[u] >> 32) != 0xFFFFFFFFu ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!fullp) {
-                        y.x = fake_quant(y.x, rf, fqlo, fqhi) * sf;
-                        y.y = fake_quant(y.y, rf, fqlo, fqhi) * sf;
-                        y.z = fake_quant(y.z, rf, fqlo, fqhi) * sf;
-                        y.w = fake_quant(y.w, rf, fqlo, fqhi) * sf;
-                    }
-                    return y;
-                };
-                if constexpr (wty) {
-                    // every row of the pass lands and is quantized before the first store goes
-                    // out: the compiler does not count an asm store, so its wait for a later row
-                    // would cover the stores issued before it (vmcnt retires in issue order)
-#pragma unroll
-                    for (int u = 0; u < FU; ++u) v[u] = quant(u);
-#pragma unroll
-                    for (int u = 0; u < FU; ++u)
-                        if (e[u] != ~0ull)
-                            st4_wt(reinterpret_cast<float4*>(outt + (int64_t)(uint32_t)e[u] * la.fwd_ost_b) + sub, v[u]);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < FU; ++u) {
-                        if (e[u] == ~0ull) continue;
-                        reinterpret_cast<float4*>(outt + (int64_t)(uint32_t)e[u] * la.fwd_ost_b)[sub] = quant(u);
-                    }
-                }
-            }
-            CDIAG_W(18);  // (diagnostic build: the next batch's forward done)
+            const float tm = ld_wt(la.tmax + t);
+            s_ftm = tm;
+            s_fok = 1;
+            __hip_atomic_store(fword, gr_make(tm, 0, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    // (i) this workgroup's lookups of the next batch -- they do not depend on the table's
+    //     final max -- as per-wave LDS lists {row | 0xFFFFFFFF, b} in lookup order (the
+    //     key region is dead by now). A dimension-split table deals its lookups round-robin
+    //     over its NA workgroups (every wave gets some); a row split takes the rows of its
+    //     own range; the last arriver also the stalled workgroups' shares.
+    int64_t nx[MAXI];
+#pragma unroll
+    for (int i = 0; i < MAXI; ++i) {
+        const int b = tid + TPB * i;
+        nx[i] = b < B ? la.fwd_idx[(int64_t)t * B + b] : -1;
+    }
+    const int me = s + SPLIT * j;
+    const uint32_t smask = s_lastarr ? (uint32_t)s_stallmask : 0u;
+    const int lane = tid % WAVE;
+    uint64_t* lst = keys + w * (WAVE * MAXI);
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < MAXI; ++i) {
+        const int b = tid + TPB * i;
+        const int64_t x = nx[i];
+        const bool okr = x >= 0 && x < nrows;
+        int own = 0;
+        if (dsplit) {
+            own = b % NA;
+        } else if (okr) {
+            const int sl = slot_of_row(x, nblk);
+            int jj = 0;
+            if (K == 2) {
+                const int64_t b0 = nblk * sl / SPLIT, b1 = nblk * (sl + 1) / SPLIT;
+                jj = (x >> 8) >= (b0 + b1) / 2 ? 1 : 0;
+            }
+            own = sl + SPLIT * jj;
+        }
+        const bool mine = b < B && ((own == me && go) || ((smask >> own) & 1u));
+        const uint64_t m = __ballot(mine);
+        if (mine) {
+            const int p = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            lst[p] = ((uint64_t)(okr ? (uint32_t)x : 0xFFFFFFFFu) << 32) | (uint32_t)b;
+            if (!okr) flag_error(a.err, DQRM_ERRF_INDEX);
+        }
+        cnt += __popcll(m);
+    }
+    CDIAG(20);
+    // (ii) a row split reads only rows it updated itself (or untouched ones): its first
+    //      rows go out now, in flight across the wait for the table's final max. Plain
+    //      loads: a workgroup's own stores are visible to it, and a dimension-split
+    //      table's rows (other workgroups' stores, one XCD) were never loaded by this CU
+    //      in this launch -- its slot ranges are block-aligned, no line is shared -- so
+    //      they come from the XCD's L2, once the wait below has ordered them.
+    const int G = LPR < WAVE ? WAVE / LPR : 1;  // rows per wave pass
+    const int gl = lane / LPR, sub = lane % LPR;
+    constexpr int FU = 4;  // rows per lane group in flight
+    uint64_t e[FU];
+    float4 v[FU];
+    auto issue = [&](int p0) {
+#pragma unroll
+        for (int u = 0; u < FU; ++u) {
+            const int ix = p0 + gl + G * u;
+            e[u] = ix < cnt && lane < G * LPR ? lst[ix] : ~0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < FU; ++u) {
+            const uint32_t x = (uint32_t)(e[u] >> 32);
+            v[u] = nrows > 0 ? reinterpret_cast<const float4*>(la.W + (rb + (x != 0xFFFFFFFFu ? x : 0u)) * a.D)[sub]
+                             : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    if (!dsplit && cnt > 0) issue(0);
+    // (iii) the table's final max: published by the last arriver (above, or at its
+    //       arrival), the others wait for it
+    if (!s_lastarr && tid == 0) {
+        // a workgroup that stalled at the rendezvous leaves its share to the last arriver
+        // and does not wait (its CU may be what a late workgroup of the table needs);
+        // the others met every workgroup of the table there, so all of them arrive
+        uint64_t gv = 0;
+        int ok = go ? 1 : 0;
+        for (uint32_t spin = 0; ok; ++spin) {
+            gv = __hip_atomic_load(fword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (gr_epoch(gv) == epoch) break;
+            if (spin > (1u << 20)) {  // (never, all resident) flagged, this share skipped
+                flag_error(a.err, DQRM_ERRF_STALL);
+                ok = 0;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        s_ftm = __uint_as_float((uint32_t)gv);
+        s_fok = ok;
+    }
+    __syncthreads();
+    CDIAG(19);
+    if (!s_fok) cnt = 0;  // (uniform)
+    const float sf = fullp ? 1.0f : (refresh ? sym_scale(s_ftm, la.fwd_bits) : la.fwd_scale[t]);
+    if (refresh && !fullp && s_lastarr && tid == 0) la.fwd_scale[t] = sf;
+    const float rf = 1.0f / sf;
+    const float fqlo = -(float)(1 << (la.fwd_bits - 1)), fqhi = (float)((1 << (la.fwd_bits - 1)) - 1);
+    float* outt = la.fwd_out + (int64_t)t * la.fwd_ost_t;
+    constexpr bool wty = (WT & WT_Y) != 0;
+    for (int p0 = 0; p0 < cnt; p0 += G * FU) {  // uniform per wave
+        if (p0 > 0 || dsplit) issue(p0);  // (the first rows of a row split went out before the wait)
+        if (p0 == 0) CDIAG_W(21);
+        auto quant = [&](int u) -> float4 {
+            float4 y = (uint32_t)(e[u] >> 32) != 0xFFFFFFFFu ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!fullp) y = fake_quant4_scaled(y, rf, fqlo, fqhi, sf);
+            return y;
+        };
+        if constexpr (wty) {
+            // every row of the pass lands and is quantized before the first store goes
+            // out: the compiler does not count an asm store, so its wait for a later row
+            // would cover the stores issued before it (vmcnt retires in issue order)
+#pragma unroll
+            for (int u = 0; u < FU; ++u) v[u] = quant(u);
+#pragma unroll
+            for (int u = 0; u < FU; ++u)
+                if (e[u] != ~0ull)
+                    st4_wt(reinterpret_cast<float4*>(outt + (int64_t)(uint32_t)e[u] * la.fwd_ost_b) + sub, v[u]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < FU; ++u) {
+                if (e[u] == ~0ull) continue;
+                reinterpret_cast<float4*>(outt + (int64_t)(uint32_t)e[u] * la.fwd_ost_b)[sub] = quant(u);
+            }
+        }
+    }
+    CDIAG_W(18);  // (diagnostic build: the next batch's forward done)
 }
 
 }  // namespace

@@ -63,6 +63,24 @@ DQRM_INLINE float fake_quant(float x, float r, float lo, float hi) {
     return t;
 }
 
+// The two float4 forms every unit's bit-exactness claim goes through.
+// The update's gradient, dqrm_apply_local's arithmetic: q = fake_quant(g); + 0.0f because the
+// payload's integer round trip turns -0 into +0.
+DQRM_INLINE float4 fake_quant4_payload(float4 v, float r, float lo, float hi) {
+    float4 q;
+    q.x = fake_quant(v.x, r, lo, hi) + 0.0f; q.y = fake_quant(v.y, r, lo, hi) + 0.0f;
+    q.z = fake_quant(v.z, r, lo, hi) + 0.0f; q.w = fake_quant(v.w, r, lo, hi) + 0.0f;
+    return q;
+}
+// The forwards' y = fake_quant(W) * s (emb_fwd_table's arithmetic), r = 1/s.
+DQRM_INLINE float4 fake_quant4_scaled(float4 v, float r, float lo, float hi, float s) {
+    v.x = fake_quant(v.x, r, lo, hi) * s;
+    v.y = fake_quant(v.y, r, lo, hi) * s;
+    v.z = fake_quant(v.z, r, lo, hi) * s;
+    v.w = fake_quant(v.w, r, lo, hi) * s;
+    return v;
+}
+
 DQRM_INLINE float abs_max4(float4 v) {
     return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
 }

@@ -504,10 +504,7 @@ __device__ __forceinline__ void emb_fwd_table(const FwdArgs& a, int t, int64_t b
                 if (full_precision) {
                     y = v;
                 } else {
-                    y.x = fake_quant(v.x, r, qlo, qhi) * s;
-                    y.y = fake_quant(v.y, r, qlo, qhi) * s;
-                    y.z = fake_quant(v.z, r, qlo, qhi) * s;
-                    y.w = fake_quant(v.w, r, qlo, qhi) * s;
+                    y = fake_quant4_scaled(v, r, qlo, qhi, s);
                 }
             }
             acc[k] = y;
@@ -653,6 +650,9 @@ __global__ void __launch_bounds__(256) k_emb_fwd_packed(FwdArgs a) {
                     const float4 w = reinterpret_cast<const float4*>(a.W + (rowbase + rr) * D)[lane];
                     v.x = v.x + w.x; v.y = v.y + w.y; v.z = v.z + w.z; v.w = v.w + w.w;
                 }
+                // fake_quant4_scaled's arithmetic, element by element into y: the same four
+                // expressions, kept in this form because it is the one this kernel's code was
+                // measured in (a call of the helper here changes the descriptor of <2, true>)
                 y.x = fake_quant(v.x, r, qlo, qhi) * s;
                 y.y = fake_quant(v.y, r, qlo, qhi) * s;
                 y.z = fake_quant(v.z, r, qlo, qhi) * s;
@@ -2105,9 +2105,7 @@ __global__ void __launch_bounds__(FLAT_TPB) k_apply_local(ApplyArgs a, const int
             if (sub == 0) flag_error(a.err, DQRM_ERRF_INDEX);
             continue;
         }
-        float4 acc;  // + 0.0f: the payload's integer round trip turns -0 into +0
-        acc.x = fake_quant(v.x, rr, qlo, qhi) + 0.0f; acc.y = fake_quant(v.y, rr, qlo, qhi) + 0.0f;
-        acc.z = fake_quant(v.z, rr, qlo, qhi) + 0.0f; acc.w = fake_quant(v.w, rr, qlo, qhi) + 0.0f;
+        const float4 acc = fake_quant4_payload(v, rr, qlo, qhi);
         const bool owned = !FIN && (xlo < 0 || (xlo >> 8) != (x >> 8)) && (xhi < 0 || (xhi >> 8) != (x >> 8));
         flat_row_update<LPR>(a, update, t, rb + x, x, nrows, bb, sbb, acc, r_pack, sub, owned, FIN ? nullptr : &oq);
     }
@@ -3597,12 +3595,7 @@ __global__ void __launch_bounds__(SG_TPB) k_sgd_small(FArgs a) {
                 const bool ok = nxr[k] >= 0 && nxr[k] < nrows;
                 if (!ok && sub == 0) flag_error(a.err, DQRM_ERRF_INDEX);
                 float4 y = ok ? v[k] : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!fullp) {
-                    y.x = fake_quant(y.x, rf, qlo, qhi) * sf;
-                    y.y = fake_quant(y.y, rf, qlo, qhi) * sf;
-                    y.z = fake_quant(y.z, rf, qlo, qhi) * sf;
-                    y.w = fake_quant(y.w, rf, qlo, qhi) * sf;
-                }
+                if (!fullp) y = fake_quant4_scaled(y, rf, qlo, qhi, sf);
                 return y;
             };
             if ((a.wt & WT_Y) != 0) {
