@@ -19,7 +19,8 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
                                                                 on the device, the AUC exact)
   * ``sgd_quantized_gradients_parallel_comm`` hooks            (INT8 sparse-grad all-reduce + SGD,
                                                                 and the MLP's per-channel INT8 grads)
-  * ``sgd_quantized_gradients`` simulated-DP buffer helpers
+  * ``sgd_quantized_gradients`` simulated-DP buffer helpers     (embedding tables and the MLP's
+                                                                error-compensated INT8 gradients)
   * ``quantized_ops.ops.quantized.embedding_bag_{4bit,byte}_*``  (row-wise PTQ inference formats)
   * ``DLRM_Net.quantize_embedding`` and the quantized ``apply_emb`` (``DQRMNet.quantize_embedding`` /
                                                                 ``RowwiseTableSet``: all tables' row-wise
@@ -30,7 +31,7 @@ from . import _lib
 from ._build import LIB_PATH, build
 from .tables import CoalescedGrad, EmbeddingTableSet, LookupBatch, default_caps, reference_scale
 from .comm import MultiSetExchange, SparseGradExchange, get_my_slice, payload_bytes
-from .dense import DenseGradExchange
+from .dense import DenseGradExchange, SimulatedDenseBuffers
 from . import quant_modules_not_quantize_grad, sgd_quantized_gradients, sgd_quantized_gradients_parallel_comm
 from .quant_modules_not_quantize_grad import QuantEmbeddingBagCollection, QuantEmbeddingBagTwo
 from .linear import QuantLinear
@@ -57,6 +58,7 @@ __all__ = [
     "get_my_slice",
     "payload_bytes",
     "DenseGradExchange",
+    "SimulatedDenseBuffers",
     "QuantEmbeddingBagTwo",
     "QuantEmbeddingBagCollection",
     "QuantLinear",

@@ -119,6 +119,8 @@ EXPORTED_SYMBOLS = (
     "dqrm_dense_grad_quant",
     "dqrm_dense_grad_decode",
     "dqrm_dense_update",
+    "dqrm_dense_ec_accumulate",
+    "dqrm_dense_sim_update",
     "dqrm_linear_wquant",
     "dqrm_linear_fwd",
     "dqrm_linear_bwd",
@@ -509,6 +511,8 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_dense_grad_quant": (C.c_int, [DS, C.c_int, P, C.c_int, P, C.c_int, P, P]),
         "dqrm_dense_grad_decode": (C.c_int, [DS, P, C.c_int, C.c_int, P]),
         "dqrm_dense_update": (C.c_int, [DS, P, C.c_float, P]),
+        "dqrm_dense_ec_accumulate": (C.c_int, [DS, C.c_int, P, P, P, P]),
+        "dqrm_dense_sim_update": (C.c_int, [DS, P, P, C.c_int, C.c_float, P]),
         "dqrm_linear_wquant": (C.c_int, [LN, P]),
         "dqrm_linear_fwd": (C.c_int, [LN, C.c_int, P, C.c_int64, P, P]),
         "dqrm_linear_bwd": (C.c_int, [LN, C.c_int, P, P, C.c_int64, P, P, P, P]),

@@ -7,6 +7,9 @@
 //   quantize_bias_grad    :931-961  the same with one scale per bias vector
 //   grad_update_parallel_comm   MLP branch :337-409  grad.zero_(); grad.add_(buffer)
 //   weight_update_parallel_comm MLP branch :630-668  W += (-lr * grad) * s
+// and of the simulated-DP buffer (sgd_quantized_gradients.py, one device playing N ranks):
+//   grad_buffer_update_added_quantization MLP branch :96-139   error-compensated INT8 accumulate
+//   weights_update_added_quantization     MLP branch :381-404  W += -lr * (buffer * (s / N))
 //
 // Design: every weight row and every bias vector of all bot_l/top_l layers is one
 // "channel"; the four phases are ONE launch each for all layers (multi-tensor style: the
@@ -133,6 +136,54 @@ __global__ void __launch_bounds__(DWG) k_dense_update(DenseArgs a, const float* 
     }
 }
 
+// One micro-step of the simulated-DP buffer with error compensation
+// (sgd_quantized_gradients.py:96-139, quantize_linear_grad / quantize_bias_grad :563-632 with
+// err_compensation=True): v = g + e; a channel whose scale is still 0 (the first micro-step
+// since zeroing) takes s = clamp(max|v|, 1e-8) / qmax; q = fake_quant(v, 1/s); buf += q;
+// e = v - q * s. The quantize pass computes g + e again (the same bits): no row is staged.
+__global__ void __launch_bounds__(DWG) k_dense_ec_accumulate(DenseArgs a, float qmax, float lo, float hi,
+                                                              float* __restrict__ scale, float* __restrict__ err,
+                                                              float* __restrict__ buf) {
+    const int c = blockIdx.x * CPW + threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    if (c >= a.C) return;
+    const float* __restrict__ g = a.grad[c];
+    const int n = a.len[c];
+    float* __restrict__ e = err + a.wire_off[c];
+    float* __restrict__ b = buf + a.wire_off[c];
+    float s = scale[c];  // the same word for the whole wave
+    if (s == 0.0f) {
+        float m0 = 0.0f, m1 = 0.0f;
+        int j = lane;
+        for (; j + WAVE < n; j += 2 * WAVE) {  // two loads of each stream in flight per lane
+            m0 = fmaxf(m0, fabsf(g[j] + e[j]));
+            m1 = fmaxf(m1, fabsf(g[j + WAVE] + e[j + WAVE]));
+        }
+        if (j < n) m0 = fmaxf(m0, fabsf(g[j] + e[j]));
+        s = fmaxf(wave_max(fmaxf(m0, m1)), 1e-8f) / qmax;
+        if (lane == 0) scale[c] = s;
+    }
+    const float rcp = 1.0f / s;
+    for (int j = lane; j < n; j += WAVE) {
+        const float v = g[j] + e[j];
+        const float q = fake_quant(v, rcp, lo, hi);
+        b[j] = b[j] + q;
+        e[j] = v - q * s;
+    }
+}
+
+// The buffer's update (sgd_quantized_gradients.py:381-404): param += -lr * (buf * (s / N)),
+// s / N a true division.
+__global__ void __launch_bounds__(DWG) k_dense_sim_update(DenseArgs a, const float* __restrict__ scale,
+                                                           const float* __restrict__ buf, float fn, float nlr) {
+    const int c = blockIdx.x * CPW + threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    if (c >= a.C) return;
+    float* __restrict__ p = a.param[c];
+    const int n = a.len[c];
+    const float* __restrict__ b = buf + a.wire_off[c];
+    const float t = scale[c] / fn;
+    for (int j = lane; j < n; j += WAVE) p[j] = p[j] + nlr * (b[j] * t);
+}
+
 int check_dense(const dqrm_dense_set* s) {
     if (!s) return set_error(DQRM_E_INVALID, "dqrm_dense: null dense set");
     if (s->num_channels < 0 || s->total_elems < 0)
@@ -254,6 +305,35 @@ int dqrm_dense_update(const dqrm_dense_set* set, const float* s, float lr, void*
     if (rc) return rc;
     if (set->num_channels == 0) return DQRM_OK;
     hipLaunchKernelGGL(k_dense_update, grid_of(set), dim3(DWG), 0, (hipStream_t)stream, args_of(set), s, -lr);
+    DQRM_HIP_TRY(hipGetLastError());
+    return DQRM_OK;
+}
+
+int dqrm_dense_ec_accumulate(const dqrm_dense_set* set, int bits, float* scale, float* err, float* buf,
+                             void* stream) {
+    int rc = check_dense(set);
+    if (rc) return rc;
+    if (bits < 2 || bits > 16)
+        return set_error(DQRM_E_INVALID, "dqrm_dense_ec_accumulate: bits must be 2..16 (got %d)", bits);
+    if (set->num_channels == 0) return DQRM_OK;
+    if (!scale || !err || !buf)
+        return set_error(DQRM_E_INVALID, "dqrm_dense_ec_accumulate: null scale, err or buf");
+    const int n = (1 << (bits - 1)) - 1;
+    hipLaunchKernelGGL(k_dense_ec_accumulate, grid_of(set), dim3(DWG), 0, (hipStream_t)stream, args_of(set),
+                       (float)n, (float)(-n - 1), (float)n, scale, err, buf);
+    DQRM_HIP_TRY(hipGetLastError());
+    return DQRM_OK;
+}
+
+int dqrm_dense_sim_update(const dqrm_dense_set* set, const float* scale, const float* buf, int num_gpus, float lr,
+                          void* stream) {
+    int rc = check_dense(set);
+    if (rc) return rc;
+    if (num_gpus < 1) return set_error(DQRM_E_INVALID, "dqrm_dense_sim_update: num_gpus < 1");
+    if (set->num_channels == 0) return DQRM_OK;
+    if (!scale || !buf) return set_error(DQRM_E_INVALID, "dqrm_dense_sim_update: null scale or buf");
+    hipLaunchKernelGGL(k_dense_sim_update, grid_of(set), dim3(DWG), 0, (hipStream_t)stream, args_of(set), scale,
+                       buf, (float)num_gpus, -lr);
     DQRM_HIP_TRY(hipGetLastError());
     return DQRM_OK;
 }

@@ -17,6 +17,10 @@ reference's 4 blocking collectives per layer become two per step:
      for N <= 16; int32 beyond), half the bytes of an FP32 gradient all-reduce.
 Kernels: dqrm_dense_grad_scale, dqrm_dense_grad_quant, dqrm_dense_grad_decode,
 dqrm_dense_update (csrc/dqrm_dense.hip).
+
+SimulatedDenseBuffers is the MLP half of the simulated-DP buffer of sgd_quantized_gradients.py
+(one device plays N ranks; error-compensated INT8 accumulate :96-139, update :381-404) over the
+same channel table: dqrm_dense_ec_accumulate and dqrm_dense_sim_update, one launch each.
 """
 from __future__ import annotations
 
@@ -154,6 +158,16 @@ class HipDenseKernels:
         L.check(self.lib.dqrm_dense_update(C.byref(self._c), _ptr(s), float(lr), _stream_handle()),
                 "dqrm_dense_update")
 
+    def ec_accumulate(self, bits, scale, err, buf):
+        L.check(self.lib.dqrm_dense_ec_accumulate(C.byref(self._c), bits, _ptr(scale), _ptr(err), _ptr(buf),
+                                                  _stream_handle()),
+                "dqrm_dense_ec_accumulate")
+
+    def sim_update(self, scale, buf, num_gpus, lr):
+        L.check(self.lib.dqrm_dense_sim_update(C.byref(self._c), _ptr(scale), _ptr(buf), int(num_gpus), float(lr),
+                                               _stream_handle()),
+                "dqrm_dense_sim_update")
+
 
 class DenseGradExchange:
     """The MLP half of grad_update_parallel_comm / weight_update_parallel_comm for all
@@ -247,6 +261,101 @@ class DenseGradExchange:
         self.kernels.update(self.s_avg if self.grad_bits != 32 else None, lr)
 
 
+class SimulatedDenseKernels(Protocol):
+    """The two device steps of SimulatedDenseBuffers (HipDenseKernels by default; CPU tests
+    inject a numpy restatement). prepare() runs before each."""
+
+    def prepare(self) -> None: ...
+
+    def ec_accumulate(self, bits: int, scale: torch.Tensor, err: torch.Tensor, buf: torch.Tensor) -> None: ...
+
+    def sim_update(self, scale: torch.Tensor, buf: torch.Tensor, num_gpus: int, lr: float) -> None: ...
+
+
+class SimulatedDenseBuffers:
+    """The MLP half of the simulated-DP buffer (sgd_quantized_gradients.py: one device plays N
+    ranks) for all bot_l + top_l QuantLinear layers, with the reference's error compensation
+    (quantize_linear_grad / quantize_bias_grad, err_compensation=True, per channel, :563-632):
+
+      accumulate()           one micro-step (:96-139): v = grad + e; a channel whose scale is 0 takes
+                             s = clamp(max|v|, 1e-8) / qmax; q = quantize(v, s); buf += q; e = v - q * s
+      update(lr, num_gpus)   (:381-404) param += -lr * (buf * (s / num_gpus))
+      zero()                 (:261-308) buf = 0, s = 0; e carries into the next window
+
+    One libdqrm launch each for accumulate (dqrm_dense_ec_accumulate) and update
+    (dqrm_dense_sim_update). The state is scale [C], err and buf [total_elems] over the
+    DenseChannels table; every layer's weight_scaling_factor, bias_scaling_factor,
+    error_compensation_weight and error_compensation_bias (its registered buffers, names
+    unchanged) and weight_grad_buffer / bias_grad_buffer (plain attributes) are views of them, so
+    they hold the live values after every call. A layer's error compensation at construction is
+    taken over. grad_bits: 8 (the reference hard-codes num_bits=8, :104-136), 2..16."""
+
+    def __init__(self, layers: Sequence[nn.Module], grad_bits: int = 8,
+                 kernels: SimulatedDenseKernels | None = None, device=None):
+        if isinstance(grad_bits, bool) or not 2 <= int(grad_bits) <= 16:
+            raise ValueError("grad_bits must be 2..16")
+        self.channels = ch = DenseChannels(layers)
+        self.grad_bits = int(grad_bits)
+        if device is None:
+            device = ch.layers[0].weight.device if ch.layers else "cpu"
+        self.device = torch.device(device)
+        self.kernels = kernels if kernels is not None else HipDenseKernels(ch, self.device)
+        self.scale = torch.zeros(ch.num_channels, dtype=torch.float32, device=self.device)
+        self.err = torch.zeros(ch.total_elems, dtype=torch.float32, device=self.device)
+        self.buf = torch.zeros(ch.total_elems, dtype=torch.float32, device=self.device)
+        self.micro_steps = 0  # accumulate() calls since zero()
+        self._views = []
+        for l, ws, bi in zip(ch.layers, ch.weight_slices, ch.bias_index):
+            w0, b0 = int(ch.wire_off[ws.start]), int(ch.wire_off[bi])
+            nw, nb = l.weight.numel(), l.bias.numel()
+            ew, eb = self.err[w0: w0 + nw].view(l.weight.shape), self.err[b0: b0 + nb]
+            for view, name in ((ew, "error_compensation_weight"), (eb, "error_compensation_bias")):
+                old = getattr(l, name, None)
+                if isinstance(old, torch.Tensor) and old.shape == view.shape:
+                    view.copy_(old)
+            self._views.append((self.scale[ws], self.scale[bi], ew, eb,
+                                self.buf[w0: w0 + nw].view(l.weight.shape), self.buf[b0: b0 + nb]))
+        self._bind()
+
+    _NAMES = ("weight_scaling_factor", "bias_scaling_factor", "error_compensation_weight",
+              "error_compensation_bias", "weight_grad_buffer", "bias_grad_buffer")
+
+    def _bind(self) -> None:
+        """Point the layers' attributes at the state (again, if something replaced one)."""
+        for l, views in zip(self.channels.layers, self._views):
+            bufs, plain = l._buffers, l.__dict__  # dict reads: nn.Module.__getattr__ costs per call
+            for name, v in zip(self._NAMES, views):
+                if (bufs[name] if name in bufs else plain.get(name)) is not v:
+                    setattr(l, name, v)
+
+    def accumulate(self) -> None:
+        for l in self.channels.layers:
+            if l.weight.grad is None or l.bias.grad is None:
+                raise ValueError("simulated DP: every QuantLinear of bot_l / top_l needs its weight and bias "
+                                 "gradient at a micro-step (call it after backward())")
+        self.kernels.prepare()
+        self.kernels.ec_accumulate(self.grad_bits, self.scale, self.err, self.buf)
+        self.micro_steps += 1
+        self._bind()
+
+    def update(self, lr: float, num_gpus: int) -> None:
+        if int(num_gpus) < 1:
+            raise ValueError("num_gpus must be >= 1")
+        self.kernels.prepare()
+        note_raw_write()  # the parameters change behind torch's version counters
+        self.kernels.sim_update(self.scale, self.buf, int(num_gpus), float(lr))
+        for l in self.channels.layers:  # what autograd saved of them is stale
+            torch.autograd.graph.increment_version(l.weight)
+            torch.autograd.graph.increment_version(l.bias)
+        self._bind()
+
+    def zero(self) -> None:
+        self.buf.zero_()
+        self.scale.zero_()
+        self.micro_steps = 0
+        self._bind()
+
+
 def _wire_type(bits: int, num_ranks: int) -> int:
     """dqrm_dense_wire_type, for host-only (injected-kernel) runs."""
     if bits == 32:
@@ -256,4 +365,5 @@ def _wire_type(bits: int, num_ranks: int) -> int:
     return L.DQRM_WIRE_F16 if num_ranks << (bits - 1) <= 2048 else L.DQRM_WIRE_I32
 
 
-__all__ = ["DenseChannels", "DenseKernels", "HipDenseKernels", "DenseGradExchange"]
+__all__ = ["DenseChannels", "DenseKernels", "HipDenseKernels", "DenseGradExchange", "SimulatedDenseKernels",
+           "SimulatedDenseBuffers"]

@@ -20,6 +20,9 @@ a ``DLRMLoss``.
 
 A model is built on its GPU (``device=``) and stays there; there is no CPU path.
 
+``micro_step`` / ``apply_micro_steps`` are the reference's simulated data parallelism (N micro-steps
+into INT8 gradient buffers, one dequantized update) for the whole model on one device.
+
 World size > 1 is out of scope of ``train_step``'s update: use ``train_step(..., update=False)``,
 which stops after the backward and leaves the gradients in ``p.grad`` and ``model.emb_grad`` for
 the package's DP hooks (``sgd_quantized_gradients_parallel_comm``) to exchange and apply.
@@ -33,11 +36,13 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from .dense import SimulatedDenseBuffers
 from .interaction import DotInteraction, out_features
 from .loss import DLRMLoss
 from .mlp import MLPStack, _on_device, create_mlp
 from .quant_modules_not_quantize_grad import error_check_due, poll_device_errors, raise_device_errors
 from .rowwise import RowwiseTableSet
+from .sgd_quantized_gradients import GRAD_BITS, _MicroStepBuffer
 from .tables import EmbeddingTableSet, LookupBatch, _stream_handle
 
 
@@ -82,8 +87,15 @@ class DQRMNet(nn.Module):
     them; ``keep_fp32=False`` releases them: ``tables`` is None and the ``emb_weight`` buffer gives
     way to ``emb_packed``, the packed slab, in ``state_dict()``.
 
+    Simulated data parallelism. ``micro_step(dense_x, batch, labels, N)`` N times, then
+    ``apply_micro_steps(lr, N)``: one device plays N ranks as the reference's pseudo-multigpu driver
+    does with ``sgd_quantized_gradients``: INT8 gradient buffers for the tables and, with error
+    compensation, for both stacks (one launch per micro-step and one per update for all MLP
+    layers). Both raise ``RuntimeError`` after ``quantize_embedding``, as ``train_step`` does.
+
     Not built: ``quantize_activation`` (``MLPStack`` does not run those layers), momentum, weight
-    decay, world size > 1 inside the step."""
+    decay, world size > 1 inside the step (one device can play N ranks: ``micro_step`` /
+    ``apply_micro_steps``)."""
 
     def __init__(self, ln_emb, m_spa, ln_bot, ln_top, sigmoid_top=None, sigmoid_bot=-1,
                  arch_interaction_itself=False, quantize_bits=None, weight_bit=4, embedding_bit=4,
@@ -147,6 +159,7 @@ class DQRMNet(nn.Module):
         self.quantize_emb = False  # quantize_embedding(): predict / evaluate read emb_q
         self.quantize_bits = None  #   its bits, 4 or 8 (the interaction's are interact.quantize_bits)
         self.emb_q = None          #   the RowwiseTableSet
+        self.emb_scaling_factor = None  # micro_step(): the tables' first-micro-step grad scales [T]
         d = self.__dict__      # plain attributes of the step (nn.Module.__setattr__ is slow per call)
         d["_ws_q"] = None      # (tensor, B): the row-wise forward's workspace, its own high-water mark
         d["_lay_q"] = None     # (L.Model, B, L.ModelLayout)
@@ -157,6 +170,8 @@ class DQRMNet(nn.Module):
         d["_lay"] = None       # (L.Model, B, max_lookups, L.ModelLayout)
         d["_last_flags"] = 0   # the DQRM_MODEL_* flags of the latest train_step
         d["_prefetched"] = None  # (batch object, tables.write_epoch, B)
+        d["_sim_emb"] = None     # micro_step(): the tables' _MicroStepBuffer
+        d["_sim_dense"] = None   #   and the stacks' SimulatedDenseBuffers
 
     # ------------------------------------------------------------ bookkeeping
     def _device(self, what):
@@ -600,6 +615,71 @@ class DQRMNet(nn.Module):
         if next_batch is not None:
             self.__dict__["_prefetched"] = (next_batch, tables.write_epoch, B)
         return loss
+
+    # ------------------------------------------------------------ simulated data parallelism
+    def micro_step(self, dense_x, batch, labels, number_of_gpus):
+        """One of the N micro-steps with which one device plays N ranks (the reference's
+        pseudo-multigpu driver with ``sgd_quantized_gradients``); returns the 0-dim loss tensor.
+
+        ``train_step(update=False)``, then this micro-step's gradients go into the INT8 buffers:
+        the embedding gradient (``model.emb_grad``) is coalesced and quantize-packed with the
+        first micro-step's max|grad| as the scale (``model.emb_scaling_factor`` ``[T]``), as
+        ``grad_buffer_update_added_quantization`` does for the modules, and the gradients of both
+        stacks' layers take ONE error-compensated accumulate (dqrm_dense_ec_accumulate; the layers'
+        ``weight_scaling_factor``, ``error_compensation_weight``, ``weight_grad_buffer`` and the
+        bias's hold the state). No parameter or table is written. ``apply_micro_steps`` applies
+        and empties the buffers."""
+        self._not_quantized("micro_step")
+        n = int(number_of_gpus)
+        if n < 1:
+            raise ValueError(f"DQRMNet.micro_step: number_of_gpus must be >= 1 (got {number_of_gpus})")
+        loss = self.train_step(dense_x, batch, labels, 0.0, update=False)
+        _on_device(self._device("micro_step"), self._micro_step, batch)
+        return loss
+
+    def _sim_buffers(self):
+        sb = self.__dict__.get("_sim_dense")
+        if sb is None:
+            sb = self.__dict__["_sim_dense"] = SimulatedDenseBuffers(self.bot_stack.layers + self.top_stack.layers,
+                                                                     grad_bits=GRAD_BITS)
+        return sb
+
+    def _micro_step(self, batch):
+        buf = _MicroStepBuffer.fitting(self.__dict__.get("_sim_emb"), self.tables, batch.max_lookups)
+        self.__dict__["_sim_emb"] = buf
+        buf.accumulate(batch, self.emb_grad, not self.embedding_full_precision, "btd")
+        self.__dict__["emb_scaling_factor"] = buf.s_first
+        self._sim_buffers().accumulate()
+
+    def apply_micro_steps(self, lr, number_of_gpus, requantize=True):
+        """The update after ``number_of_gpus`` micro-steps (``weights_update_added_quantization``
+        then ``grad_buffer_zeroing``): the tables take W += -lr * (buffer * (s / N))
+        (dqrm_apply_sparse_update, DQRM_UPD_SIMULATED), every MLP parameter
+        p += -lr * (buffer * (s[c] / N)) in ONE launch (dqrm_dense_sim_update), and both buffers
+        and their scales are zeroed (the MLP's error compensation carries into the next window).
+        Raises ``ValueError`` unless exactly ``number_of_gpus`` micro-steps were accumulated. The
+        stacks are stale afterwards; requantize=True (default) calls ``requantize()``, so that the
+        next window's forwards skip the weight quantization."""
+        self._not_quantized("apply_micro_steps")
+        dev = self._device("apply_micro_steps")
+        buf = self.__dict__.get("_sim_emb")
+        if buf is None or len(buf.payloads) != int(number_of_gpus):
+            raise ValueError(f"{0 if buf is None else len(buf.payloads)} micro-steps accumulated but "
+                             f"num_gpus={number_of_gpus}")
+        _on_device(dev, self._apply_micro_steps, buf, float(lr), int(number_of_gpus), bool(requantize))
+
+    def _apply_micro_steps(self, buf, lr, n, requantize):
+        sb = self._sim_buffers()
+        self.bot_stack._fresh = self.top_stack._fresh = None
+        self.__dict__["_prefetched"] = None
+        self.tables.write_epoch += 1
+        buf.apply(lr, n, False)
+        sb.update(lr, n)
+        buf.zero()
+        buf.s_first.zero_()
+        sb.zero()
+        if requantize:
+            self.requantize()
 
 
 __all__ = ["DQRMNet"]

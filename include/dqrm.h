@@ -97,7 +97,10 @@ extern "C" {
                                   dqrm_rowwise_set_fwd, dqrm_model_fwd_rowwise,
                                   dqrm_model_fwd_rowwise_workspace_bytes,
                                   dqrm_model_fwd_rowwise_workspace_layout,
-                                  dqrm_model_fwd_rowwise_launches */
+                                  dqrm_model_fwd_rowwise_launches;
+                                  likewise within 12: the MLP half of the simulated-DP buffer
+                                  (sgd_quantized_gradients): dqrm_dense_ec_accumulate,
+                                  dqrm_dense_sim_update */
 
 /* status codes */
 #define DQRM_OK            0
@@ -595,6 +598,28 @@ int dqrm_dense_grad_decode(const dqrm_dense_set* set, const void* wire, int wire
 /* weight_update_parallel_comm, MLP branch (:641-642 / :659-660):
  *   param += (-lr * grad) * s[c]     (s == NULL: param += -lr * grad, :644-645). */
 int dqrm_dense_update(const dqrm_dense_set* set, const float* s, float lr, void* stream);
+
+/* Simulated DP (one device plays N ranks, sgd_quantized_gradients.py): the MLP half of
+ * grad_buffer_update_added_quantization (:96-139) with the error compensation of
+ * quantize_linear_grad / quantize_bias_grad (:563-632, err_compensation=True, per channel).
+ * One micro-step, ONE launch for all channels; scale [C], err and buf [total_elems] laid out by
+ * wire_off, every operation a separately rounded f32 one:
+ *   v = grad + err
+ *   scale[c] == 0 (first micro-step since zeroing):
+ *       scale[c] = clamp(max_j |v_j|, 1e-8) / (2^(bits-1)-1)      (quant_utils.py:196-220)
+ *   q   = clamp(round(1/scale[c] * v + 0), -2^(bits-1), 2^(bits-1)-1)   (quant_utils.py:75-101, 316-346)
+ *   buf = buf + q
+ *   err = v - q * scale[c]
+ * A scale once set is >= 1e-8/qmax > 0, so scale[c] == 0 is the reference's host-side
+ * "sum of the tensor's scales is zero" test with no host read. Zeroing (:261-308) is the
+ * caller's: buf = 0 and scale = 0; err carries over. bits 2..16 (the reference hard-codes 8). */
+int dqrm_dense_ec_accumulate(const dqrm_dense_set* set, int bits, float* scale, float* err, float* buf,
+                             void* stream);
+
+/* weights_update_added_quantization, MLP branch (:381-404), ONE launch:
+ *   param = param + (-lr) * (buf * (scale[c] / num_gpus))    (scale / N a true f32 division) */
+int dqrm_dense_sim_update(const dqrm_dense_set* set, const float* scale, const float* buf, int num_gpus,
+                          float lr, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * QuantLinear: the fake-quantized MLP layer (quantization_supp/
