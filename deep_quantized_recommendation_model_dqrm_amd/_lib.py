@@ -136,11 +136,19 @@ EXPORTED_SYMBOLS = (
     "dqrm_mlp_sgd",
     "dqrm_mlp_sgd_multi_workspace_bytes",
     "dqrm_mlp_sgd_multi",
+    "dqrm_mlp_qact_prepare",
+    "dqrm_mlp_fwd_qact",
+    "dqrm_mlp_bwd_qact",
     "dqrm_model_workspace_bytes",
     "dqrm_model_workspace_layout",
     "dqrm_model_fwd",
     "dqrm_model_step",
     "dqrm_model_step_launches",
+    "dqrm_model_qact_workspace_bytes",
+    "dqrm_model_qact_workspace_layout",
+    "dqrm_model_fwd_qact",
+    "dqrm_model_step_qact",
+    "dqrm_model_qact_step_launches",
     "dqrm_metrics_reset",
     "dqrm_metrics_update",
     "dqrm_metrics_workspace_bytes",
@@ -331,6 +339,16 @@ class Model(C.Structure):
     ]
 
 
+class ModelQAct(C.Structure):
+    """Mirror of ``dqrm_model_qact`` (include/dqrm.h): the QuantActs beside a ``dqrm_model``."""
+
+    _fields_ = [
+        ("quant_input", C.POINTER(ActQuant)),
+        ("quant_features", C.POINTER(ActQuant)),
+        ("out_scale", C.POINTER(C.c_void_p)),
+    ]
+
+
 class ModelLayout(C.Structure):
     """Mirror of ``dqrm_model_layout`` (include/dqrm.h): byte offsets into the workspace."""
 
@@ -427,6 +445,7 @@ def load(path: str | None = None) -> C.CDLL:
     PP = C.POINTER(C.c_void_p)  # a host array of device pointers
     MO = C.POINTER(Model)
     MS = C.POINTER(ML)  # a host array of stacks
+    MQ = C.POINTER(ModelQAct)
     RS = C.POINTER(RowwiseSet)
     sig = {
         "dqrm_refresh_absmax": (C.c_int, [TS, P]),
@@ -528,11 +547,21 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_mlp_sgd": (C.c_int, [ML, C.c_uint32, PP, PP, PP, C.c_float, P, C.c_size_t, P]),
         "dqrm_mlp_sgd_multi_workspace_bytes": (C.c_size_t, [MS, C.c_int]),
         "dqrm_mlp_sgd_multi": (C.c_int, [MS, C.c_int, C.c_uint32, PP, PP, PP, C.c_float, P, C.c_size_t, P]),
+        "dqrm_mlp_qact_prepare": (C.c_int, [ML, P, PP, P]),
+        "dqrm_mlp_fwd_qact": (C.c_int, [ML, C.c_uint32, P, P, PP, C.c_int64, PP, P]),
+        "dqrm_mlp_bwd_qact": (C.c_int, [ML, P, PP, P, P, PP, C.c_int64, P, PP, PP, P, C.c_size_t, P]),
         "dqrm_model_workspace_bytes": (C.c_size_t, [MO, C.c_int64, C.c_int64]),
         "dqrm_model_workspace_layout": (C.c_int, [MO, C.c_int64, C.c_int64, C.POINTER(ModelLayout)]),
         "dqrm_model_fwd": (C.c_int, [MO, BA, C.c_uint32, P, P, P, P, P, C.c_size_t, P]),
         "dqrm_model_step": (C.c_int, [MO, BA, BA, C.c_uint32, P, P, C.c_float, P, P, P, PP, PP, P, C.c_size_t, P]),
         "dqrm_model_step_launches": (C.c_int, [MO, BA, BA, C.c_uint32]),
+        "dqrm_model_qact_workspace_bytes": (C.c_size_t, [MO, MQ, C.c_int64, C.c_int64]),
+        "dqrm_model_qact_workspace_layout": (C.c_int, [MO, MQ, C.c_int64, C.c_int64, C.POINTER(ModelLayout)]),
+        "dqrm_model_fwd_qact": (C.c_int, [MO, MQ, BA, C.c_uint32, P, P, P, P, P, C.c_size_t, P]),
+        "dqrm_model_step_qact": (
+            C.c_int, [MO, MQ, BA, BA, C.c_uint32, P, P, C.c_float, P, P, P, PP, PP, P, C.c_size_t, P]
+        ),
+        "dqrm_model_qact_step_launches": (C.c_int, [MO, MQ, BA, BA, C.c_uint32]),
         "dqrm_metrics_reset": (C.c_int, [C.POINTER(Metrics), P]),
         "dqrm_metrics_update": (C.c_int, [C.POINTER(Metrics), P, P, C.c_int64, C.c_int64, P]),
         "dqrm_metrics_workspace_bytes": (C.c_size_t, [C.c_int64]),

@@ -177,6 +177,19 @@ int partial_groups(int64_t numel) {
 
 }  // namespace
 
+int dqrm_internal::check_act_quant(const dqrm_act_quant* q, const char* what) {
+    if (!q) return set_error(DQRM_E_INVALID, "%s: null dqrm_act_quant", what);
+    if (q->activation_bit < 2 || q->activation_bit > 32)
+        return set_error(DQRM_E_INVALID, "%s: activation_bit must be 2..32 (got %d)", what, q->activation_bit);
+    if (!q->x_min || !q->x_max || !q->scale) return set_error(DQRM_E_INVALID, "%s: null x_min / x_max / scale", what);
+    return DQRM_OK;
+}
+
+int dqrm_internal::act_quant_fwd_launches(const dqrm_act_quant* q, int64_t numel) {
+    if (numel <= 0) return 0;
+    return 1 + (q->running_stat ? 1 + (partial_groups(numel) > 0 ? 1 : 0) : 0);
+}
+
 extern "C" {
 
 int64_t dqrm_act_quant_workspace_bytes(int64_t numel) {
@@ -187,10 +200,8 @@ int64_t dqrm_act_quant_workspace_bytes(int64_t numel) {
 int dqrm_act_quant_fwd(const dqrm_act_quant* q, const float* x, int64_t numel, float* y, void* workspace,
                        void* stream) {
     const char* what = "dqrm_act_quant_fwd";
-    if (!q) return set_error(DQRM_E_INVALID, "%s: null dqrm_act_quant", what);
-    if (q->activation_bit < 2 || q->activation_bit > 32)
-        return set_error(DQRM_E_INVALID, "%s: activation_bit must be 2..32 (got %d)", what, q->activation_bit);
-    if (!q->x_min || !q->x_max || !q->scale) return set_error(DQRM_E_INVALID, "%s: null x_min / x_max / scale", what);
+    int rc = dqrm_internal::check_act_quant(q, what);
+    if (rc) return rc;
     if (numel < 0) return set_error(DQRM_E_INVALID, "%s: negative numel", what);
     if (numel == 0) return DQRM_OK;
     if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);

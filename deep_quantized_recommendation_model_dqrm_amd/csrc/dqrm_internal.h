@@ -94,6 +94,14 @@ DQRM_HIDDEN int check_act(int act, const char* who);
 // tensor (the fused SGD + requantize then takes a second launch and a workspace).
 DQRM_HIDDEN int check_mlp(const dqrm_mlp* m, const char* who);
 DQRM_HIDDEN bool has_tensor_layer(const dqrm_mlp* m);
+// what dqrm_mlp_fwd_qact / _bwd_qact / _qact_prepare reject beyond check_mlp: a full-precision
+// layer, per_channel anywhere but on the last layer, a null prev, out_scale array or entry
+DQRM_HIDDEN int check_mlp_qact(const dqrm_mlp* m, const float* prev, float* const* out_scale, const char* who);
+
+// dqrm_act.hip: the struct as dqrm_act_quant_fwd rejects it, and that call's launches for numel
+// elements with a y (3, 2 or 1: see include/dqrm.h)
+DQRM_HIDDEN int check_act_quant(const dqrm_act_quant* q, const char* who);
+DQRM_HIDDEN int act_quant_fwd_launches(const dqrm_act_quant* q, int64_t numel);
 
 // dqrm_kernels.hip, for the whole-model step (dqrm_model.hip), which validates its embedding
 // stage before its first launch: everything dqrm_emb_fwd and dqrm_emb_bwd_sgd / _sgd_fwd reject,

@@ -4,9 +4,12 @@
 // dqrm_mlp_fwd / dqrm_mlp_bwd hold no GEMM code: they validate the whole stack and then call the
 // per-layer exports of dqrm_linear.hip (dqrm_linear_wquant, dqrm_linear_fwd_act,
 // dqrm_linear_bwd_act) in the order a layer-by-layer caller would, so their bits are those calls'
-// bits by construction. What they save is the host's work per layer.
+// bits by construction. What they save is the host's work per layer. dqrm_mlp_fwd_qact /
+// dqrm_mlp_bwd_qact are the same over the integer-activation exports (dqrm_linear_*_qact), with
+// k_mlp_qact_prepare (below) in the place of the per-layer weight quantization while the stack's
+// integers are current.
 //
-// dqrm_mlp_sgd is the new kernel. Reference (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM
+// dqrm_mlp_sgd is the update kernel. Reference (YangZhou08/Deep_Quantized_Recommendation_Model_DQRM
 // @ 2024-10-24): sgd_quantized_gradients_parallel_comm.py:642-646 (the MLP branch of
 // weight_update_parallel_comm) and the quantization half of QuantLinear.forward
 // (quantization_supp/quant_modules_not_quantize_grad.py:121-154), i.e. what dqrm_dense_update and
@@ -142,6 +145,50 @@ __global__ void __launch_bounds__(SWG) k_mlp_requant_tensor(SgdArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------ qact prepare
+// The activation-scale half of dqrm_linear_wquant_qact for every layer of a stack whose weight
+// integers and scales are current (dqrm_linear.hip's quant_bias<true>, q_m_n_q_g.py:150-154):
+//     p_0 = prev[0];  p_(l+1) = scale_l[0] * p_l          (layer l's one-element out_scale)
+//     c[o] = scale_l[o] * p_l;  out_scale_l[o] = c[o];  bias_integer_l[o] = fake_quant(b_l[o], 1 / c[o])
+// Workgroups are dealt to layers by the prefix of their counts in the kernel arguments; a
+// workgroup's layer is uniform, so its chain of at most 15 products is scalar loads and scalar
+// multiplications, each separately rounded, and the same chain the per-layer calls hand from one
+// out_scale to the next. One thread per output. Nothing is read that this launch writes.
+constexpr int PWG = 256;            // threads (outputs) per workgroup
+
+struct QactLayer {
+    const float* b;       // [out]
+    const float* scale;   // [out] per channel, [1] per tensor: current (the caller's promise)
+    float* bi;            // [out] bias_integer
+    float* cos;           // [out] / [1] out_scale
+    float blo, bhi;       // bias clamp
+    int out;
+    int per_channel;
+    int blk0;             // the layer's first workgroup in the grid
+};
+
+struct QactArgs {
+    QactLayer layer[DQRM_MLP_MAX_LAYERS];
+    int num_layers;
+    const float* prev;    // [1] the activation scale in front of the stack
+};
+
+__global__ void __launch_bounds__(PWG) k_mlp_qact_prepare(QactArgs a) {
+    const int blk = blockIdx.x;
+    int l = 0;
+    while (l + 1 < a.num_layers && blk >= a.layer[l + 1].blk0) ++l;
+    float p = a.prev[0];
+    for (int j = 0; j < l; ++j) p = a.layer[j].scale[0] * p;
+    const QactLayer& d = a.layer[l];
+    const int o = (blk - d.blk0) * PWG + (int)threadIdx.x;
+    if (o >= d.out) return;
+    const float s = d.per_channel ? d.scale[o] : d.scale[0];
+    const float c = s * p;
+    if (d.per_channel) d.cos[o] = c;
+    else if (o == 0) d.cos[0] = c;
+    d.bi[o] = fake_quant(d.b[o], 1.0f / c, d.blo, d.bhi);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ validation
@@ -173,9 +220,31 @@ bool dqrm_internal::has_tensor_layer(const dqrm_mlp* m) {
     return false;
 }
 
+// an integer-activation stack: every layer quantized (the reference's scale chain breaks at a
+// full-precision layer: its forward returns no scale), only the last one per channel (a [out]
+// out_scale cannot be the next layer's one-element prev), the scale in front and one out_scale each
+int dqrm_internal::check_mlp_qact(const dqrm_mlp* m, const float* prev, float* const* out_scale, const char* what) {
+    int rc = check_mlp(m, what);
+    if (rc) return rc;
+    for (int i = 0; i < m->num_layers; ++i) {
+        if (!m->quantized[i])
+            return set_error(DQRM_E_INVALID, "%s: layer %d is full precision: an integer-activation stack's scale "
+                                             "chain needs every layer quantized", what, i);
+        if (m->layers[i].per_channel && i + 1 < m->num_layers)
+            return set_error(DQRM_E_INVALID, "%s: layer %d is per_channel: only the last layer may be (its out_scale "
+                                             "is the next layer's one-element prev)", what, i);
+    }
+    if (!prev) return set_error(DQRM_E_INVALID, "%s: null prev", what);
+    if (!out_scale) return set_error(DQRM_E_INVALID, "%s: null out_scale array", what);
+    for (int i = 0; i < m->num_layers; ++i)
+        if (!out_scale[i]) return set_error(DQRM_E_INVALID, "%s: null out_scale[%d]", what, i);
+    return DQRM_OK;
+}
+
 namespace {
 
 using dqrm_internal::check_mlp;
+using dqrm_internal::check_mlp_qact;
 using dqrm_internal::has_tensor_layer;
 
 int check_flags(uint32_t flags, uint32_t known, const char* what) {
@@ -312,6 +381,64 @@ int sgd_stacks(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, co
     return launch_sgd(a, two, (hipStream_t)stream);
 }
 
+// dqrm_mlp_bwd (prev == out_scale == NULL) and dqrm_mlp_bwd_qact on a stack already checked
+int stack_bwd(const dqrm_mlp* m, const float* x, const float* const* y, const float* dy, const float* prev,
+              float* const* out_scale, int64_t B, float* dx, float* const* dw, float* const* db, void* scratch,
+              size_t scratch_bytes, void* stream, const char* what) {
+    int rc;
+    if (B < 1 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!x || !dy) return set_error(DQRM_E_INVALID, "%s: null x / dy", what);
+    const int L = m->num_layers;
+    if ((rc = check_ptrs((const void* const*)y, L, "y", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
+    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
+    const size_t half = (size_t)B * (size_t)max_hidden(m) * sizeof(float);
+    if (half && (!scratch || scratch_bytes < 2 * half))
+        return set_error(DQRM_E_INVALID, "%s: scratch of %zu bytes, dqrm_mlp_bwd_scratch_bytes asks for %zu", what,
+                         scratch ? scratch_bytes : (size_t)0, 2 * half);
+    float* buf[2] = {(float*)scratch, (float*)((char*)scratch + half)};
+    for (int i = L - 1; i >= 0; --i) {
+        // layer i's dx is layer i-1's dy: buf[i & 1] is written while buf[(i + 1) & 1] is read
+        const float* dyi = i == L - 1 ? dy : buf[(i + 1) & 1];
+        float* dxi = i == 0 ? dx : buf[i & 1];
+        const float* xi = i ? y[i - 1] : x;
+        if (out_scale)
+            rc = dqrm_linear_bwd_qact(&m->layers[i], m->act[i], xi, y[i], dyi, i ? out_scale[i - 1] : prev,
+                                      out_scale[i], B, dxi, dw[i], db[i], stream);
+        else
+            rc = dqrm_linear_bwd_act(&m->layers[i], m->quantized[i] != 0, m->act[i], xi, y[i], dyi, B, dxi, dw[i],
+                                     db[i], stream);
+        if (rc) return rc;
+    }
+    return DQRM_OK;
+}
+
+// the prepare launch for a stack check_mlp_qact passed
+int launch_qact_prepare(const dqrm_mlp* m, const float* prev, float* const* out_scale, hipStream_t st) {
+    QactArgs a{};
+    int blk = 0;
+    for (int i = 0; i < m->num_layers; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        const int64_t nb = ((int64_t)1 << (l->bias_bit - 1)) - 1;
+        QactLayer& d = a.layer[i];
+        d.b = l->bias;
+        d.scale = l->scale;
+        d.bi = l->bias_integer;
+        d.cos = out_scale[i];
+        d.blo = (float)(-nb - 1);
+        d.bhi = (float)nb;
+        d.out = l->out_features;
+        d.per_channel = l->per_channel != 0;
+        d.blk0 = blk;
+        blk += (l->out_features + PWG - 1) / PWG;
+    }
+    a.num_layers = m->num_layers;
+    a.prev = prev;
+    hipLaunchKernelGGL(k_mlp_qact_prepare, dim3((unsigned)blk), dim3(PWG), 0, st, a);
+    DQRM_HIP_TRY(hipGetLastError());
+    return DQRM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -345,26 +472,47 @@ int dqrm_mlp_bwd(const dqrm_mlp* m, const float* x, const float* const* y, const
     const char* what = "dqrm_mlp_bwd";
     int rc = check_mlp(m, what);
     if (rc) return rc;
-    if (B < 1 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
-    if (!x || !dy) return set_error(DQRM_E_INVALID, "%s: null x / dy", what);
-    const int L = m->num_layers;
-    if ((rc = check_ptrs((const void* const*)y, L, "y", what))) return rc;
-    if ((rc = check_ptrs((const void* const*)dw, L, "dw", what))) return rc;
-    if ((rc = check_ptrs((const void* const*)db, L, "db", what))) return rc;
-    const size_t half = (size_t)B * (size_t)max_hidden(m) * sizeof(float);
-    if (half && (!scratch || scratch_bytes < 2 * half))
-        return set_error(DQRM_E_INVALID, "%s: scratch of %zu bytes, dqrm_mlp_bwd_scratch_bytes asks for %zu", what,
-                         scratch ? scratch_bytes : (size_t)0, 2 * half);
-    float* buf[2] = {(float*)scratch, (float*)((char*)scratch + half)};
-    for (int i = L - 1; i >= 0; --i) {
-        // layer i's dx is layer i-1's dy: buf[i & 1] is written while buf[(i + 1) & 1] is read
-        const float* dyi = i == L - 1 ? dy : buf[(i + 1) & 1];
-        float* dxi = i == 0 ? dx : buf[i & 1];
-        if ((rc = dqrm_linear_bwd_act(&m->layers[i], m->quantized[i] != 0, m->act[i], i ? y[i - 1] : x, y[i], dyi, B,
-                                      dxi, dw[i], db[i], stream)))
+    return stack_bwd(m, x, y, dy, nullptr, nullptr, B, dx, dw, db, scratch, scratch_bytes, stream, what);
+}
+
+int dqrm_mlp_qact_prepare(const dqrm_mlp* m, const float* prev, float* const* out_scale, void* stream) {
+    int rc = check_mlp_qact(m, prev, out_scale, "dqrm_mlp_qact_prepare");
+    if (rc) return rc;
+    return launch_qact_prepare(m, prev, out_scale, (hipStream_t)stream);
+}
+
+int dqrm_mlp_fwd_qact(const dqrm_mlp* m, uint32_t flags, const float* x, const float* prev, float* const* out_scale,
+                      int64_t B, float* const* y, void* stream) {
+    const char* what = "dqrm_mlp_fwd_qact";
+    int rc = check_mlp_qact(m, prev, out_scale, what);
+    if (rc) return rc;
+    if ((rc = check_flags(flags, DQRM_MLP_FRESH, what))) return rc;
+    if (B < 0 || B > INT32_MAX) return set_error(DQRM_E_INVALID, "%s: bad batch size", what);
+    if (!y) return set_error(DQRM_E_INVALID, "%s: null y array", what);
+    if (B > 0) {
+        if (!x) return set_error(DQRM_E_INVALID, "%s: null x", what);
+        if ((rc = check_ptrs((const void* const*)y, m->num_layers, "y", what))) return rc;
+    }
+    // B == 0: the out_scales and bias integers are still written, no GEMM is launched
+    const bool fresh = (flags & DQRM_MLP_FRESH) != 0;
+    if (fresh && (rc = launch_qact_prepare(m, prev, out_scale, (hipStream_t)stream))) return rc;
+    for (int i = 0; i < m->num_layers; ++i) {
+        const dqrm_linear* l = &m->layers[i];
+        const float* p = i ? out_scale[i - 1] : prev;
+        if (!fresh && (rc = dqrm_linear_wquant_qact(l, p, out_scale[i], stream))) return rc;
+        if (B > 0 && (rc = dqrm_linear_fwd_qact(l, m->act[i], i ? y[i - 1] : x, p, out_scale[i], B, y[i], stream)))
             return rc;
     }
     return DQRM_OK;
+}
+
+int dqrm_mlp_bwd_qact(const dqrm_mlp* m, const float* x, const float* const* y, const float* dy, const float* prev,
+                      float* const* out_scale, int64_t B, float* dx, float* const* dw, float* const* db,
+                      void* scratch, size_t scratch_bytes, void* stream) {
+    const char* what = "dqrm_mlp_bwd_qact";
+    int rc = check_mlp_qact(m, prev, out_scale, what);
+    if (rc) return rc;
+    return stack_bwd(m, x, y, dy, prev, out_scale, B, dx, dw, db, scratch, scratch_bytes, stream, what);
 }
 
 size_t dqrm_mlp_sgd_workspace_bytes(const dqrm_mlp* m) {

@@ -18,7 +18,8 @@ A model built by the reference's own create_mlp is converted in place:
 ``MLPStack`` runs a fused stack as a whole: one host call for its forward, one for its backward
 (dqrm_mlp_fwd / dqrm_mlp_bwd, which issue the per-layer launches), and ``sgd_step``, one launch
 that updates every layer and requantizes it, so the next forward launches no quantization: the
-same step goes from 27 launches plus the optimizer's to 22.
+same step goes from 27 launches plus the optimizer's to 22. A ``quantize_activation`` stack runs the
+same way on dqrm_mlp_fwd_qact / dqrm_mlp_bwd_qact: ``y, out_scale = stack(x, prev_act_scaling_factor)``.
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .linear import _ACTS, QuantLinear, _check_input, raw_write_epoch
+from .linear import _ACTS, MissingActScale, QuantLinear, _check_input, raw_write_epoch
 from .tables import _stream_handle
 
 _KINDS = {"relu": nn.ReLU, "sigmoid": nn.Sigmoid}
@@ -178,6 +179,47 @@ class _StackFn(torch.autograd.Function):
         return (dx, None, None, None, *dws, *dbs)
 
 
+class _StackQActFn(torch.autograd.Function):
+    """_StackFn for a quantize_activation stack: one dqrm_mlp_fwd_qact and one dqrm_mlp_bwd_qact.
+    ``scales`` are the fresh correct_output_scale tensors the forward writes, one per layer; the
+    backward reads them and the saved ``prev``."""
+
+    @staticmethod
+    def forward(ctx, x, stack, c, fresh, prev, scales, *params):
+        B = x.shape[0]
+        ys = [torch.empty((B, l.out_features), dtype=torch.float32, device=x.device) for l in stack.layers]
+        A = stack._PtrArray
+        L.check(stack._lib.dqrm_mlp_fwd_qact(C.byref(c), L.DQRM_MLP_FRESH if fresh else 0, x.data_ptr(),
+                                             prev.data_ptr(), A(*[s.data_ptr() for s in scales]), B,
+                                             A(*[y.data_ptr() for y in ys]), _stream_handle()), "dqrm_mlp_fwd_qact")
+        ctx.save_for_backward(x, prev, *scales, *ys)
+        ctx.stack = stack
+        return ys[-1]
+
+    @staticmethod
+    def backward(ctx, dy):
+        stack = ctx.stack
+        layers = stack.layers
+        n = len(layers)
+        x, prev, *rest = ctx.saved_tensors
+        scales, ys = rest[:n], rest[n:]
+        dy = dy.contiguous()
+        B = x.shape[0]
+        dws = [torch.empty_like(l.weight) for l in layers]
+        dbs = [torch.empty_like(l.bias) for l in layers]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        if B == 0:
+            return (dx, None, None, None, None, None, *[t.zero_() for t in dws], *[t.zero_() for t in dbs])
+        scratch = torch.empty(2 * B * stack._max_hidden, dtype=torch.float32, device=x.device)
+        A = stack._PtrArray
+        L.check(stack._lib.dqrm_mlp_bwd_qact(C.byref(stack._c_struct()), x.data_ptr(), A(*[y.data_ptr() for y in ys]),
+                                             dy.data_ptr(), prev.data_ptr(), A(*[s.data_ptr() for s in scales]), B,
+                                             None if dx is None else dx.data_ptr(), A(*[t.data_ptr() for t in dws]),
+                                             A(*[t.data_ptr() for t in dbs]), scratch.data_ptr(),
+                                             scratch.numel() * 4, _stream_handle()), "dqrm_mlp_bwd_qact")
+        return (dx, None, None, None, None, None, *dws, *dbs)
+
+
 class MLPStack:
     """A ``create_mlp`` stack run as a whole: ``stack(x)`` is one host call each way
     (dqrm_mlp_fwd / dqrm_mlp_bwd, the per-layer launches and bits of ``apply_mlp``), and
@@ -203,8 +245,17 @@ class MLPStack:
     The one hole: an in-place write through ``.data`` (``p.data.add_()``) does not bump
     ``p._version``; after such a write call ``invalidate()``.
 
-    Not built: ``quantize_activation`` layers (their bias is quantized with a scale that changes
-    every forward), momentum, weight decay and other optimizers."""
+    ``quantize_activation`` stacks (every layer quantized and built with
+    ``quantize_activation=True``; only the last may be ``per_channel``) are called as ``apply_mlp``
+    threads them: ``y, out_scale = stack(x, prev_act_scaling_factor)``, one dqrm_mlp_fwd_qact and
+    one dqrm_mlp_bwd_qact. "Fresh" then means that the weight integers and ``fc_scaling_factor``
+    are current: ``bias_integer`` and ``correct_output_scale`` depend on the activation scale and
+    are rewritten by every forward, in ONE launch for all layers while the stack is fresh
+    (dqrm_mlp_qact_prepare). ``sgd_step``, ``requantize`` and ``invalidate`` are the same calls.
+
+    Not built: the CPU description of a ``quantize_activation`` stack (such a stack must be built
+    from layers on a GPU; NotImplementedError otherwise), momentum, weight decay and other
+    optimizers."""
 
     def __init__(self, layers):
         self.module_list = layers  # the list the stack is bound to, left as it is
@@ -227,18 +278,34 @@ class MLPStack:
         for i, l in enumerate(self.layers):
             if "weight" not in l._parameters:
                 raise RuntimeError(f"layer {i}: QuantLinear.set_param(linear) has not been called")
-            if l.quantize_activation and not l.full_precision_flag:
-                raise NotImplementedError("MLPStack does not run quantize_activation=True layers: their bias is "
-                                          "quantized with a scale that changes every forward; use apply_mlp")
             if i and l.in_features != self.layers[i - 1].out_features:
                 raise ValueError(f"layer {i} takes {l.in_features} features but layer {i - 1} returns "
                                  f"{self.layers[i - 1].out_features}")
         n = len(self.layers)
+        # an integer-activation stack: its quantized layers all take a prev_act_scaling_factor
+        self._qact = any(l.quantize_activation and not l.full_precision_flag for l in self.layers)
+        if self._qact:
+            self._check_qact()
+            if any(l.weight.device.type != "cuda" for l in self.layers):
+                raise NotImplementedError("MLPStack: the CPU description of a quantize_activation=True stack is "
+                                          "not built; move the layers to a GPU first")
         self._PtrArray = C.c_void_p * n
         self._max_hidden = max([l.out_features for l in self.layers[:-1]], default=0)
         self._c = None          # (key, L.MLP, the ctypes arrays it points into)
         self._fresh = None      # the freshness record, or None
         self._workspace = None  # dqrm_mlp_sgd's row maxima (per-tensor layers), allocated once
+
+    def _check_qact(self):
+        """What dqrm_mlp_fwd_qact rejects in the layers' settings, as Python errors."""
+        for i, l in enumerate(self.layers):
+            if l.full_precision_flag or not l.quantize_activation:
+                raise ValueError(f"MLPStack: layer {i} is {'full precision' if l.full_precision_flag else 'weight-only'}"
+                                 " in a quantize_activation stack: the activation scale is handed from layer to "
+                                 "layer, so every layer must be quantized with quantize_activation=True")
+            if l.per_channel and i + 1 < len(self.layers):
+                raise ValueError(f"MLPStack: layer {i} is per_channel in a quantize_activation stack: only the last "
+                                 "layer may be (a per-channel correct_output_scale cannot feed the next layer, in "
+                                 "the reference either)")
 
     # ------------------------------------------------------------ the C view of the stack
     @property
@@ -274,8 +341,8 @@ class MLPStack:
                     raise Exception("For weight, we only support symmetric quantization.")
                 if l.quant_mode != "symmetric":
                     raise ValueError("unknown quant mode: {}".format(l.quant_mode))
-                if l.quantize_activation:
-                    raise NotImplementedError("MLPStack does not run quantize_activation=True layers")
+                if bool(l.quantize_activation) != self._qact:
+                    raise ValueError(f"MLPStack: layer {i}'s quantize_activation changed since the stack was built")
                 if l.bias_bit is None:
                     raise TypeError("QuantLinear quantizes its bias: bias_bit must be an int")
             a = getattr(l, "activation", None)
@@ -314,11 +381,30 @@ class MLPStack:
         caller that has just computed it)."""
         return self._fresh is not None and self._fresh == self._state(key)
 
-    def __call__(self, x):
+    def __call__(self, x, prev_act_scaling_factor=None):
+        """``y``; for a quantize_activation stack ``(y, out_scale)``, the last layer's
+        correct_output_scale, from ``prev_act_scaling_factor``, the one-element scale of the
+        QuantAct in front of the stack."""
         self._prepare(x)
-        return _on_device(x.device, self._run, x)
+        prev = prev_act_scaling_factor
+        if not self._qact:
+            if prev is not None:
+                raise NotImplementedError("a prev_act_scaling_factor on a stack without quantize_activation=True "
+                                          "layers is not built (the reference's drivers never pass one)")
+        else:
+            if prev is None:
+                raise MissingActScale("MLPStack: a quantize_activation stack needs a prev_act_scaling_factor "
+                                      "(QuantAct's act_scaling_factor)")
+            if not isinstance(prev, torch.Tensor) or prev.numel() != 1:
+                got = tuple(prev.shape) if isinstance(prev, torch.Tensor) else type(prev).__name__
+                raise ValueError(f"prev_act_scaling_factor must be a tensor of ONE element (got {got})")
+            if prev.dtype != torch.float32 or prev.device != x.device:
+                raise ValueError(f"prev_act_scaling_factor must be float32 on the input's device (got {prev.dtype} "
+                                 f"on {prev.device})")
+            self._check_qact()
+        return _on_device(x.device, self._run, x, prev)
 
-    def _run(self, x):
+    def _run(self, x, prev=None):
         key = self._key()
         c = self._c_struct(key)  # raises on an unsupported layer before autograd is involved
         fresh = self.is_fresh(key)
@@ -326,7 +412,16 @@ class MLPStack:
             self._fresh = None
         ws = [l.weight for l in self.layers]
         bs = [l.bias for l in self.layers]
-        return _StackFn.apply(x, self, c, fresh, *ws, *bs)
+        if not self._qact:
+            return _StackFn.apply(x, self, c, fresh, *ws, *bs)
+        # [1, O] / [1, 1] as QuantLinear leaves them; fresh per forward, so the scales an earlier
+        # forward saved for its backward are never overwritten
+        scales = [torch.empty((1, l.out_features if l.per_channel else 1), dtype=torch.float32, device=x.device)
+                  for l in self.layers]
+        y = _StackQActFn.apply(x, self, c, fresh, prev.detach(), scales, *ws, *bs)
+        for l, s in zip(self.layers, scales):
+            l._buffers["correct_output_scale"] = s
+        return y, scales[-1]
 
     # ------------------------------------------------------------ the update
     def sgd_step(self, lr, requantize=True, grad_scales=None):

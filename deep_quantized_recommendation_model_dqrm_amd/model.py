@@ -36,6 +36,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from .act import QuantAct
 from .dense import SimulatedDenseBuffers
 from .interaction import DotInteraction, out_features
 from .loss import DLRMLoss
@@ -93,7 +94,21 @@ class DQRMNet(nn.Module):
     compensation, for both stacks (one launch per micro-step and one per update for all MLP
     layers). Both raise ``RuntimeError`` after ``quantize_embedding``, as ``train_step`` does.
 
-    Not built: ``quantize_activation`` (``MLPStack`` does not run those layers), momentum, weight
+    ``quantize_activation=True`` (the drivers' ``--quantize_activation``) adds ``quant_input`` and
+    ``quant_feature_outputs`` (``QuantAct``, under the reference's attribute names, activation_bit =
+    max(weight_bit, 8), act_range_momentum=-1) in front of the two stacks, whose layers take their
+    integer-activation branch; ``forward`` composes them and ``train_step`` / ``predict`` /
+    ``evaluate`` run dqrm_model_step_qact / dqrm_model_fwd_qact. The QuantActs' ``x_min``, ``x_max``
+    and ``act_scaling_factor`` are written in place by those calls, and ``running_stat`` is whatever
+    the modules say (``fix()`` / ``unfix()``): like the reference's test loop, ``predict`` and
+    ``evaluate`` keep updating a running range. Stacks of more than one layer must be per tensor
+    (``ValueError`` for ``per_channel=True``: the reference cannot run that either). With
+    ``full_precision_flag=True`` the QuantActs stand in front of full-precision stacks (the
+    reference's act-only branch). ``micro_step`` / ``apply_micro_steps`` and ``quantize_embedding``
+    raise ``NotImplementedError`` on such a model, and its CPU description is not built
+    (``device="cpu"`` raises ``NotImplementedError``).
+
+    Not built: momentum, weight
     decay, world size > 1 inside the step (one device can play N ranks: ``micro_step`` /
     ``apply_micro_steps``)."""
 
@@ -103,9 +118,10 @@ class DQRMNet(nn.Module):
                  quantize_activation=False, loss_function="bce", loss_weights=None, loss_threshold=0.0,
                  device="cuda", emb_weights=None):
         super().__init__()
-        if quantize_activation:
-            raise NotImplementedError("DQRMNet does not run quantize_activation=True: MLPStack has no "
-                                      "integer-activation form (use apply_mlp with QuantAct)")
+        self.quantize_activation = bool(quantize_activation)
+        if quantize_activation and torch.device(device).type != "cuda":
+            raise NotImplementedError("DQRMNet: the CPU description of a quantize_activation=True model is not "
+                                      "built; build it with device='cuda'")
         self.ln_emb = [int(n) for n in np.asarray(ln_emb).reshape(-1)]
         self.m_spa = int(m_spa)
         self.ln_bot = [int(n) for n in np.asarray(ln_bot).reshape(-1)]
@@ -134,10 +150,20 @@ class DQRMNet(nn.Module):
             raise ValueError("emb_weights needs one tensor per table")
         if sigmoid_top is None:
             sigmoid_top = len(self.ln_top) - 2
+        if quantize_activation:
+            if per_channel and not full_precision_flag and max(len(self.ln_bot), len(self.ln_top)) > 2:
+                raise ValueError("DQRMNet(quantize_activation=True): stacks of more than one layer must quantize "
+                                 "per tensor (per_channel=False): a per-channel correct_output_scale cannot feed the "
+                                 "next layer, in the reference either")
+            # dlrm_s_pytorch_tb_dp_one_parallel_comm.py:475-476, under the reference's attribute names
+            abit = weight_bit if weight_bit >= 8 else 8
+            self.quant_input = QuantAct(activation_bit=abit, act_range_momentum=-1)
+            self.quant_feature_outputs = QuantAct(fixed_point_quantization=True, activation_bit=abit,
+                                                  act_range_momentum=-1)
         self.bot_l = create_mlp(self.ln_bot, sigmoid_bot, weight_bit=weight_bit, full_precision_flag=full_precision_flag,
-                                per_channel=per_channel)
+                                per_channel=per_channel, quantize_activation=self.quantize_activation)
         self.top_l = create_mlp(self.ln_top, sigmoid_top, weight_bit=weight_bit, full_precision_flag=full_precision_flag,
-                                per_channel=per_channel)
+                                per_channel=per_channel, quantize_activation=self.quantize_activation)
         self.interact = DotInteraction(arch_interaction_itself, quantize_bits)
         self.loss = DLRMLoss(loss_function, loss_weights, loss_threshold)
         self.tables = None
@@ -148,6 +174,9 @@ class DQRMNet(nn.Module):
             self.top_l.to(dev)
             self.interact.to(dev)
             self.loss.to(dev)
+            if quantize_activation:
+                self.quant_input.to(dev)
+                self.quant_feature_outputs.to(dev)
             assert want == out_features(T + 1, D, arch_interaction_itself)
         else:  # a description only: every compute path raises DQRMError
             self.register_buffer("emb_weight", torch.cat([w.float() for w in emb_weights]), persistent=True)
@@ -172,6 +201,7 @@ class DQRMNet(nn.Module):
         d["_prefetched"] = None  # (batch object, tables.write_epoch, B)
         d["_sim_emb"] = None     # micro_step(): the tables' _MicroStepBuffer
         d["_sim_dense"] = None   #   and the stacks' SimulatedDenseBuffers
+        d["_cq"] = None          # quantize_activation: (key, L.ModelQAct, what it points into)
 
     # ------------------------------------------------------------ bookkeeping
     def _device(self, what):
@@ -255,6 +285,55 @@ class DQRMNet(nn.Module):
         self.__dict__["_cm"] = (key, m, (cb, ct, lc, tc))
         return m
 
+    def _c_qact(self, dev):
+        """The dqrm_model_qact beside the model struct: the two QuantActs over their own buffers
+        (x_min, x_max and act_scaling_factor are written in place) and one persistent
+        correct_output_scale per layer, bound as the layers' buffer."""
+        qs = (self.quant_input, self.quant_feature_outputs)
+        layers = self.bot_stack.layers + self.top_stack.layers
+        for q in qs:
+            if q.full_precision_flag or q.quant_mode != "symmetric" or q.act_percentile != 0:
+                raise NotImplementedError("DQRMNet: the one-call paths run symmetric QuantActs with "
+                                          "full_precision_flag=False and act_percentile=0")
+            for name in ("x_min", "x_max", "act_scaling_factor"):
+                t = getattr(q, name)
+                if t.device != dev or t.dtype != torch.float32 or t.numel() != 1:
+                    raise ValueError(f"QuantAct.{name} must be one float32 on the model's device {dev}")
+        integer = self.bot_stack._qact  # False: QuantActs in front of full-precision stacks
+        if integer:
+            for l in layers:  # [1, O] / [1, 1], as the layer's own forward leaves the buffer
+                n = l.out_features if l.per_channel else 1
+                t = l.correct_output_scale
+                if tuple(t.shape) != (1, n) or t.device != dev or t.dtype != torch.float32:
+                    l._buffers["correct_output_scale"] = torch.ones((1, n), dtype=torch.float32, device=dev)
+        key = tuple((q.x_min.data_ptr(), q.x_max.data_ptr(), q.act_scaling_factor.data_ptr(), int(q.activation_bit),
+                     bool(q.running_stat), float(q.act_range_momentum)) for q in qs) \
+            + (tuple(l.correct_output_scale.data_ptr() for l in layers) if integer else ())
+        ent = self.__dict__["_cq"]
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        cs = []
+        for q in qs:
+            c = L.ActQuant()
+            c.activation_bit = int(q.activation_bit)
+            c.running_stat = int(bool(q.running_stat))
+            c.momentum = float(q.act_range_momentum)
+            c.one_minus_momentum = 1.0 - float(q.act_range_momentum)  # as QuantAct._run rounds it
+            c.x_min, c.x_max, c.scale = q.x_min.data_ptr(), q.x_max.data_ptr(), q.act_scaling_factor.data_ptr()
+            cs.append(c)
+        qa = L.ModelQAct()
+        qa.quant_input, qa.quant_features = C.pointer(cs[0]), C.pointer(cs[1])
+        arr = None
+        if integer:
+            arr = (C.c_void_p * len(layers))(*[l.correct_output_scale.data_ptr() for l in layers])
+            qa.out_scale = arr
+        self.__dict__["_cq"] = (key, qa, (cs, arr))
+        return qa
+
+    def _qa_only(self, what):
+        if self.quantize_activation:
+            raise NotImplementedError(f"DQRMNet.{what} is not built for a quantize_activation=True model")
+
     def _prepare(self, what):
         """The stacks' checks, their keys and the model struct."""
         if self.loss.loss_function == "wbce" and self.loss.loss_ws.device != self._device(what):
@@ -273,7 +352,10 @@ class DQRMNet(nn.Module):
             return ent[0]
         hb = max(B, ent[1]) if ent is not None else B
         hl = max(max_lookups, ent[2]) if ent is not None else max_lookups
-        need = self.tables.lib.dqrm_model_workspace_bytes(C.byref(m), hb, hl)
+        if self.quantize_activation:
+            need = self.tables.lib.dqrm_model_qact_workspace_bytes(C.byref(m), C.byref(self._c_qact(dev)), hb, hl)
+        else:
+            need = self.tables.lib.dqrm_model_workspace_bytes(C.byref(m), hb, hl)
         if need == 0:
             L.check(L.DQRM_E_INVALID, "dqrm_model_workspace_bytes")
         ws = torch.zeros(need, dtype=torch.uint8, device=dev)
@@ -290,6 +372,7 @@ class DQRMNet(nn.Module):
         if ent is not None and ent[0] is m and ent[1] == B and ent[2] == max_lookups:
             return ent[3]
         lay = L.ModelLayout()
+        # the quantize_activation cut starts with this one, at the same offsets
         L.check(self.tables.lib.dqrm_model_workspace_layout(C.byref(m), B, max_lookups, C.byref(lay)),
                 "dqrm_model_workspace_layout")
         self.__dict__["_lay"] = (m, B, max_lookups, lay)
@@ -350,6 +433,7 @@ class DQRMNet(nn.Module):
         gather from ``model.emb_q``. Any other ``bits`` raises ``ValueError`` (the reference prints
         nothing and returns). keep_fp32=False releases the FP32 tables (see the class docstring).
         Calling it again on a model that kept its FP32 tables repacks them with the new bits."""
+        self._qa_only("quantize_embedding")
         if isinstance(bits, bool) or bits not in (4, 8):
             raise ValueError(f"DQRMNet.quantize_embedding: bits must be 4 or 8, got {bits!r}")
         if self.tables is None and self.emb_q is not None:
@@ -439,13 +523,20 @@ class DQRMNet(nn.Module):
         layout="btd")`` takes; the stacks are updated with ``sgd_step``."""
         self._not_quantized("forward")
         self._device("forward")
-        x = self.bot_stack(dense_x)
+        qa = self.quantize_activation
+        integer = qa and self.bot_stack._qact  # False: QuantActs in front of full-precision stacks
+        if qa:
+            dense_x, s_in = self.quant_input(dense_x)
+        x = self.bot_stack(dense_x, s_in)[0] if integer else self.bot_stack(dense_x)
         slab = self.tables.forward(batch, bits=self.embedding_bit, refresh_scale=True,
                                    full_precision=self.embedding_full_precision, layout="btd")
         if torch.is_grad_enabled():
             slab.requires_grad_(True)
         self.emb_out = slab
-        return self.top_stack(self.interact(x, slab))
+        r = self.interact(x, slab)
+        if qa:
+            r, s_feat = self.quant_feature_outputs(r)
+        return self.top_stack(r, s_feat)[0] if integer else self.top_stack(r)
 
     # ------------------------------------------------------------ one host call
     def predict(self, dense_x, batch, labels=None):
@@ -467,10 +558,14 @@ class DQRMNet(nn.Module):
         if labels is not None:
             loss = torch.empty((), dtype=torch.float32, device=dev)
             z = torch.empty((B, 1), dtype=torch.float32, device=dev)
-        L.check(self.tables.lib.dqrm_model_fwd(
-            C.byref(m), C.byref(batch.c), L.DQRM_MODEL_MLP_FRESH if fresh else 0, dense_x.data_ptr(),
-            None if labels is None else labels.data_ptr(), None if loss is None else loss.data_ptr(),
-            None if z is None else z.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle()), "dqrm_model_fwd")
+        tail = (C.byref(batch.c), L.DQRM_MODEL_MLP_FRESH if fresh else 0, dense_x.data_ptr(),
+                None if labels is None else labels.data_ptr(), None if loss is None else loss.data_ptr(),
+                None if z is None else z.data_ptr(), ws.data_ptr(), ws.numel(), _stream_handle())
+        if self.quantize_activation:
+            L.check(self.tables.lib.dqrm_model_fwd_qact(C.byref(m), C.byref(self._c_qact(dev)), *tail),
+                    "dqrm_model_fwd_qact")
+        else:
+            L.check(self.tables.lib.dqrm_model_fwd(C.byref(m), *tail), "dqrm_model_fwd")
         if labels is not None:
             return loss, z
         return self._view(ws, m, B, batch.max_lookups, "p").clone()
@@ -546,8 +641,12 @@ class DQRMNet(nn.Module):
             fresh = self.bot_stack.is_fresh() and self.top_stack.is_fresh()
         flags = (L.DQRM_MODEL_MLP_FRESH if fresh else 0) | (L.DQRM_MODEL_REQUANT if update else L.DQRM_MODEL_NO_UPDATE) \
             | (L.DQRM_MODEL_EMB_READY if prefetched else 0)
-        n = self.tables.lib.dqrm_model_step_launches(C.byref(m), C.byref(batch.c),
-                                                     None if next_batch is None else C.byref(next_batch.c), flags)
+        nb = None if next_batch is None else C.byref(next_batch.c)
+        if self.quantize_activation:
+            qa = self._c_qact(self._device("step_launches"))
+            n = self.tables.lib.dqrm_model_qact_step_launches(C.byref(m), C.byref(qa), C.byref(batch.c), nb, flags)
+        else:
+            n = self.tables.lib.dqrm_model_step_launches(C.byref(m), C.byref(batch.c), nb, flags)
         if n < 0:
             L.check(n, "dqrm_model_step_launches")
         return n
@@ -598,11 +697,14 @@ class DQRMNet(nn.Module):
         self._poll()
         if update:  # whatever happens from here on, the integers are no longer known to be current
             bot._fresh = top._fresh = None
-        rc = tables.lib.dqrm_model_step(
-            C.byref(m), C.byref(batch.c), None if next_batch is None else C.byref(next_batch.c), flags,
-            dense_x.data_ptr(), labels.data_ptr(), lr, loss.data_ptr(), z.data_ptr(), g.data_ptr(), dw, db,
-            ws.data_ptr(), ws.numel(), _stream_handle())
-        L.check(rc, "dqrm_model_step")
+        tail = (C.byref(batch.c), None if next_batch is None else C.byref(next_batch.c), flags,
+                dense_x.data_ptr(), labels.data_ptr(), lr, loss.data_ptr(), z.data_ptr(), g.data_ptr(), dw, db,
+                ws.data_ptr(), ws.numel(), _stream_handle())
+        if self.quantize_activation:
+            L.check(tables.lib.dqrm_model_step_qact(C.byref(m), C.byref(self._c_qact(dev)), *tail),
+                    "dqrm_model_step_qact")
+        else:
+            L.check(tables.lib.dqrm_model_step(C.byref(m), *tail), "dqrm_model_step")
         self.__dict__["z"] = z
         self.__dict__["emb_grad"] = self._view(ws, m, B, batch.max_lookups, "demb")
         if not update:
@@ -629,6 +731,7 @@ class DQRMNet(nn.Module):
         ``weight_scaling_factor``, ``error_compensation_weight``, ``weight_grad_buffer`` and the
         bias's hold the state). No parameter or table is written. ``apply_micro_steps`` applies
         and empties the buffers."""
+        self._qa_only("micro_step")
         self._not_quantized("micro_step")
         n = int(number_of_gpus)
         if n < 1:
@@ -660,6 +763,7 @@ class DQRMNet(nn.Module):
         Raises ``ValueError`` unless exactly ``number_of_gpus`` micro-steps were accumulated. The
         stacks are stale afterwards; requantize=True (default) calls ``requantize()``, so that the
         next window's forwards skip the weight quantization."""
+        self._qa_only("apply_micro_steps")
         self._not_quantized("apply_micro_steps")
         dev = self._device("apply_micro_steps")
         buf = self.__dict__.get("_sim_emb")

@@ -100,7 +100,13 @@ extern "C" {
                                   dqrm_model_fwd_rowwise_launches;
                                   likewise within 12: the MLP half of the simulated-DP buffer
                                   (sgd_quantized_gradients): dqrm_dense_ec_accumulate,
-                                  dqrm_dense_sim_update */
+                                  dqrm_dense_sim_update;
+                                  likewise within 12: quantize_activation models on the stack and
+                                  the whole-model calls, dqrm_model_qact: dqrm_mlp_qact_prepare,
+                                  dqrm_mlp_fwd_qact, dqrm_mlp_bwd_qact, dqrm_model_fwd_qact,
+                                  dqrm_model_step_qact, dqrm_model_qact_workspace_bytes,
+                                  dqrm_model_qact_workspace_layout,
+                                  dqrm_model_qact_step_launches */
 
 /* status codes */
 #define DQRM_OK            0
@@ -741,7 +747,8 @@ int dqrm_linear_bwd_qact(const dqrm_linear* layer, int act, const float* x, cons
  * A whole MLP stack (create_mlp's QuantLinear layers with their fused activations) per host
  * call, csrc/dqrm_mlp.hip. The struct and its three arrays are HOST memory; the pointers inside
  * each dqrm_linear, and the entries of every pointer array below, are device pointers.
- * Weight-only layers: there is no integer-activation (quantize_activation) form.
+ * dqrm_mlp_fwd / _bwd run weight-only layers; dqrm_mlp_fwd_qact / _bwd_qact below are their
+ * integer-activation (quantize_activation) forms.
  * ------------------------------------------------------------------------------ */
 #define DQRM_MLP_MAX_LAYERS 16   /* the update kernel takes the layer descriptors by value */
 typedef struct dqrm_mlp {
@@ -807,6 +814,42 @@ size_t dqrm_mlp_sgd_multi_workspace_bytes(const dqrm_mlp* const* stacks, int num
 int dqrm_mlp_sgd_multi(const dqrm_mlp* const* stacks, int num_stacks, uint32_t flags, const float* const* dw,
                        const float* const* db, const float* const* gscale, float lr, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* The integer-activation (quantize_activation) stack: every layer runs dqrm_linear_*_qact, layer
+ * i's prev being `prev` (one float, the QuantAct's scale in front of the stack) for i == 0 and
+ * out_scale[i-1] otherwise. out_scale: HOST array of L device pointers, out_scale[i] is [1], or
+ * [out_i] for a per-channel layer; the forward WRITES them and the backward reads them.
+ *
+ * dqrm_mlp_qact_prepare, ONE launch for all layers: the half of dqrm_linear_wquant_qact that
+ * depends on the activation scale. With p_0 = prev[0] and p_(i+1) = scale_i[0] * p_i:
+ *   out_scale_i[o]    = scale_i[o] * p_i             (scale_i[0] without per_channel)
+ *   bias_integer_i[o] = clamp(rintf(1 / out_scale_i[o] * b_i[o] + 0))     to bias_bit
+ * each a separately rounded f32 operation: bit for bit what L calls of dqrm_linear_wquant_qact
+ * leave in out_scale and bias_integer. It READS the layers' scale, so it is valid only while
+ * scale and weight_integer are current (dqrm_mlp_sgd with DQRM_MLP_REQUANT, or a wquant, since the
+ * last write to the weights). No atomics, no workgroup waits on another.
+ *
+ * dqrm_mlp_fwd_qact: with DQRM_MLP_FRESH one prepare launch, then dqrm_linear_fwd_qact per layer
+ * (L + 1 launches); without it dqrm_linear_wquant_qact and dqrm_linear_fwd_qact per layer. B == 0:
+ * the out_scales and bias integers are still written, no GEMM runs.
+ * dqrm_mlp_bwd_qact: dqrm_linear_bwd_qact from layer L-1 to layer 0 with dqrm_mlp_bwd's two
+ * scratch buffers (dqrm_mlp_bwd_scratch_bytes) and launch counts.
+ *
+ * dqrm_mlp_sgd and _multi are unchanged: with DQRM_MLP_REQUANT they write bias_integer with the
+ * WEIGHT's scale, which is not what an integer-activation layer reads; the next forward's prepare
+ * (or wquant_qact) overwrites it before any GEMM does. scale and weight_integer are what they
+ * keep current for such a stack.
+ *
+ * DQRM_E_INVALID before any launch: everything dqrm_mlp_fwd / _bwd reject; a layer with
+ * quantized[i] == 0 (the reference's scale chain breaks there); per_channel on any layer but the
+ * last (an [out] out_scale cannot be the next layer's one-element prev); a null prev, out_scale
+ * array or entry. */
+int dqrm_mlp_qact_prepare(const dqrm_mlp* stack, const float* prev, float* const* out_scale, void* stream);
+int dqrm_mlp_fwd_qact(const dqrm_mlp* stack, uint32_t flags, const float* x, const float* prev,
+                      float* const* out_scale, int64_t B, float* const* y, void* stream);
+int dqrm_mlp_bwd_qact(const dqrm_mlp* stack, const float* x, const float* const* y, const float* dy,
+                      const float* prev, float* const* out_scale, int64_t B, float* dx, float* const* dw,
+                      float* const* db, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * QuantAct: fake-quantized activations with a running range (quantization_supp/
@@ -1061,6 +1104,63 @@ int dqrm_model_step(const dqrm_model* model, const dqrm_batch* batch, const dqrm
                     float* const* dw, float* const* db, void* workspace, size_t workspace_bytes, void* stream);
 int dqrm_model_step_launches(const dqrm_model* model, const dqrm_batch* batch, const dqrm_batch* next,
                              uint32_t flags);
+
+/* The quantize_activation model (--quantize_activation, DLRM_Net's quant_input and
+ * quant_feature_outputs, dlrm_s_pytorch_tb_dp_one_parallel_comm.py:475-476, :845-876): the calls
+ * above with a QuantAct in front of each stack and the stacks' integer-activation forms. The set
+ * below is HOST memory and stands beside the model; dqrm_model itself is unchanged. No arithmetic
+ * here either: the same shared bodies call the stage exports.
+ *
+ * Forward: dqrm_emb_fwd; dqrm_act_quant_fwd(quant_input, x -> xq); dqrm_mlp_fwd_qact(bottom, xq,
+ * prev = quant_input->scale, out_scale); dqrm_interact_scale / _fwd -> r;
+ * dqrm_act_quant_fwd(quant_features, r -> rq); dqrm_mlp_fwd_qact(top, rq, prev =
+ * quant_features->scale, out_scale + L_bottom); dqrm_loss_fwd.
+ * Backward: dqrm_mlp_bwd_qact(top) with dx; dqrm_act_quant_bwd(quant_features->scale) on it ->
+ * dr; dqrm_interact_bwd; dqrm_mlp_bwd_qact(bottom, dx == NULL) -- quant_input's input is data and
+ * gets no backward launch --; dqrm_emb_bwd_sgd[_fwd]; dqrm_mlp_sgd_multi. flags, next and
+ * DQRM_MODEL_NO_UPDATE mean what they mean above; DQRM_MODEL_MLP_FRESH promises current scales
+ * and weight integers, and each stack's forward is then one dqrm_mlp_qact_prepare and its GEMMs.
+ * The QuantActs' x_min / x_max / scale are WRITTEN as dqrm_act_quant_fwd writes them
+ * (running_stat as each struct says).
+ *
+ * Act-only mode (the reference's branch at :845-851, QuantActs in front of full-precision MLPs):
+ * when every layer of both stacks has quantized[i] == 0 the stacks run dqrm_mlp_fwd / _bwd on
+ * xq / rq and out_scale is not read (it may be NULL). A mixture of quantized and full-precision
+ * layers is rejected.
+ *
+ * Workspace: dqrm_model_qact_workspace_bytes; dqrm_model_step's cut comes first, at its offsets
+ * (dqrm_model_qact_workspace_layout reports the same members, `total` the longer size), then
+ * xq [B][in_bottom], rq [B][R], the two dqrm_act_quant workspaces and the [B][R] gradient in
+ * front of quant_features' backward.
+ *
+ * dqrm_model_qact_step_launches: dqrm_model_step_launches' count with, for integer stacks, the
+ * not-fresh weight quantization per layer as there (1 per channel, 2 per tensor) and, fresh, + 2
+ * (one prepare per stack); + the two QuantAct forwards (each 1 without running_stat, 2 up to
+ * 16384 elements, 3 above) + 1 for quant_features' backward. Fresh per-tensor stacks of L layers
+ * in all, a plain interaction and DQRM_MODEL_REQUANT: 3L + a_in + a_feat + 9.
+ *
+ * DQRM_E_INVALID before any launch: everything the calls above reject; a null set or QuantAct;
+ * what dqrm_act_quant_fwd rejects in either struct; for integer stacks what dqrm_mlp_fwd_qact
+ * rejects (per_channel on any layer but a stack's last, a null out_scale array or entry). */
+typedef struct dqrm_model_qact {
+    const dqrm_act_quant* quant_input;     /* in front of the bottom stack */
+    const dqrm_act_quant* quant_features;  /* quant_feature_outputs, in front of the top stack */
+    float* const* out_scale;               /* HOST [L_bottom + L_top] device pointers: bottom's layers, then top's */
+} dqrm_model_qact;
+
+size_t dqrm_model_qact_workspace_bytes(const dqrm_model* model, const dqrm_model_qact* qact, int64_t B,
+                                       int64_t max_lookups);
+int dqrm_model_qact_workspace_layout(const dqrm_model* model, const dqrm_model_qact* qact, int64_t B,
+                                     int64_t max_lookups, dqrm_model_layout* out);
+int dqrm_model_fwd_qact(const dqrm_model* model, const dqrm_model_qact* qact, const dqrm_batch* batch,
+                        uint32_t flags, const float* x, const float* labels, float* loss, float* z,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int dqrm_model_step_qact(const dqrm_model* model, const dqrm_model_qact* qact, const dqrm_batch* batch,
+                         const dqrm_batch* next, uint32_t flags, const float* x, const float* labels, float lr,
+                         float* loss, float* z, float* g, float* const* dw, float* const* db, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int dqrm_model_qact_step_launches(const dqrm_model* model, const dqrm_model_qact* qact, const dqrm_batch* batch,
+                                  const dqrm_batch* next, uint32_t flags);
 
 /* ---------------------------------------------------------------------------------
  * DLRMMetrics: the two numbers of the reference's test loop, test accuracy and ROC AUC
