@@ -14,8 +14,9 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC_DIR = os.path.join(PKG_DIR, "csrc")
-SOURCES = [os.path.join(CSRC_DIR, f) for f in ("dqrm_kernels.hip", "dqrm_coalesce.hip", "dqrm_dense.hip",
-                                                "dqrm_input.hip", "dqrm_sync.hip", "dqrm_exchange.hip", "dqrm_lookup.hip",
+SOURCES = [os.path.join(CSRC_DIR, f) for f in ("dqrm_kernels.hip", "dqrm_coalesce.hip", "dqrm_host.hip",
+                                                "dqrm_tables.hip", "dqrm_dense.hip", "dqrm_input.hip",
+                                                "dqrm_sync.hip", "dqrm_exchange.hip", "dqrm_lookup.hip",
                                                 "dqrm_comm.hip", "dqrm_apply.hip", "dqrm_apply_merge.hip",
                                                 "dqrm_linear.hip", "dqrm_interact.hip", "dqrm_act.hip", "dqrm_loss.hip",
                                                 "dqrm_mlp.hip", "dqrm_model.hip", "dqrm_metrics.hip",

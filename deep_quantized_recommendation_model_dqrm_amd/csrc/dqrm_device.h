@@ -230,6 +230,13 @@ DQRM_INLINE void pack4_row(const float4 w, uint8_t* __restrict__ prow, int idx4,
     reinterpret_cast<uint16_t*>(prow)[idx4] = pack4_int4(q0, q1, q2, q3);
 }
 
+// the same for lane `lane` of the LPR lanes on slab row grow
+template <int LPR>
+DQRM_INLINE void pack_row_int4(const float4 w, uint8_t* __restrict__ packed, int64_t grow,
+                               int lane, float r) {
+    pack4_row(w, packed + grow * (LPR * 2), lane, r);
+}
+
 // Per table, after its slot workgroups: re-reduce flagged superblocks, then tmax over all
 // superblocks. Narrow tables (<= 256 rows, dimension-split in the slot kernels) get their
 // rowmax, block, superblock and table maxima rebuilt from W here (<= 256 rows x D floats),

@@ -1,6 +1,7 @@
 // dqrm_exchange.hip — the N > 1 exchange step's quantize-pack (K5): the rank's coalesced
 // gradient (slot workspace) -> its dense wire payload, with the table scales averaged over
-// the ranks' all-gathered per-slot max|grad|.
+// the ranks' all-gathered per-slot max|grad|. The whole stage: both kernels, the launcher and
+// the dqrm_grad_quant_pack* exports.
 //
 // Reference: sgd_quantized_gradients_parallel_comm.py quantize_emb_grad :861-869
 //   s_r = clamp(max|g|, 1e-8) / (2^(b-1) - 1)            (quant_utils.py:141-194)
@@ -19,7 +20,35 @@
 #include "dqrm_device.h"
 #include "dqrm_internal.h"
 
+namespace dqrm_internal {
+
+// K5 quantize-pack of the N > 1 exchange (k_qpack): the rank's slot workspace ->
+// its wire payload, the table scales averaged over the all-gathered per-slot maxima
+// (dqrm_grad_quant_pack_strided's arguments, validated by the caller).
+struct QuantPackArgs {
+    int T;
+    int D;
+    const int64_t* ws_cap_base;  // [T*S+1]
+    const int32_t* ws_rows;
+    const float* ws_vals;
+    const int32_t* ws_ucount;
+    const float* absmax_all;     // [N][pitch], rank r's per-slot max|grad| at r*pitch + t*S + s
+    int64_t am_pitch;
+    int N;
+    int bits;                    // 2..16 quantized, 32 = FP32 values
+    const int64_t* cap_base;     // [T+1] payload capacity prefix
+    int64_t cap_total;
+    float* s_avg;                // [T]
+    unsigned char* payload;
+    uint32_t wt;                 // wt_stores() bits (WT_HAND: the payload values write-through)
+};
+
+}  // namespace dqrm_internal
+
 namespace {
+
+using dqrm_internal::QuantPackArgs;
+using dqrm_internal::set_error;
 
 constexpr int SPLIT = DQRM_TABLE_SPLIT;
 constexpr int QP_TPB = 256;
@@ -133,13 +162,9 @@ __global__ void __launch_bounds__(QP_TPB) k_qpack(dqrm_internal::QuantPackArgs a
     }
 }
 
-}  // namespace
-
-namespace dqrm_internal {
-
 hipError_t launch_quant_pack(const QuantPackArgs& a0, hipStream_t stream) {
     QuantPackArgs a = a0;
-    a.wt = wt_stores(a.D);
+    a.wt = dqrm_internal::wt_stores(a.D);
     // chunks per slot: the payload capacity spread evenly over the slots (a Criteo batch's
     // rows land roughly evenly in a table's row ranges), at least 1, at most 16
     const int64_t slots = (int64_t)a.T * SPLIT;
@@ -162,4 +187,180 @@ hipError_t launch_quant_pack(const QuantPackArgs& a0, hipStream_t stream) {
     return hipGetLastError();
 }
 
-}  // namespace dqrm_internal
+// ------------------------------------------------------------------------------------
+// The earlier K5 (DQRM_QPACK=legacy, A/B) and the ranking range's pack, which has no other kernel.
+// ------------------------------------------------------------------------------------
+// One workgroup per (table, slot): the table's 8 slot counts are clamped in slot order
+// against the table's payload capacity (overflow truncates the table), the N ranks'
+// per-slot max|grad| are staged in LDS and averaged in Gloo's order, then LPR lanes per
+// entry quantize and store the slot's entries at their dense payload position. Workgroup
+// (t, 0) also writes the table's header counts and s_avg[t].
+template <int LPR>
+__global__ void __launch_bounds__(512) k_quant_pack(int T, const int64_t* __restrict__ ws_cap_base,
+                                                    int64_t ws_cap_total, const int32_t* __restrict__ ws_rows,
+                                                    const float* __restrict__ ws_vals,
+                                                    const int32_t* __restrict__ ws_ucount,
+                                                    const float* __restrict__ absmax_all, int64_t am_pitch,
+                                                    int N, int bits,
+                                                    const int64_t* __restrict__ cap_base, int64_t cap_total,
+                                                    float* __restrict__ s_avg, unsigned char* __restrict__ payload,
+                                                    const int32_t* __restrict__ tbits,
+                                                    const float* __restrict__ tscale) {
+    __shared__ int s_cnt[SPLIT];
+    __shared__ float s_am[64 * SPLIT];
+    __shared__ int s_pre, s_my;
+    __shared__ float s_sc;
+    (void)ws_cap_total;
+    const int k = blockIdx.x, t = k / SPLIT, s = k % SPLIT;
+    const int D = LPR * 4;
+    const PayloadLayout pl = payload_layout(T, cap_total, D, bits);
+    // ranking range (tbits != NULL): per-table bit width and scale; 0 / 32-bit tables send
+    // nothing (grad_update_parallel_comm skips them, s_q_g_p_c.py:280-289)
+    const int tb = tbits ? tbits[t] : bits;
+    const bool ranked = tbits != nullptr;
+    const bool send = !ranked || (tb >= 2 && tb <= 8);
+    const bool quant = !ranked && bits >= 2 && bits <= 16;
+    if (threadIdx.x < SPLIT) s_cnt[threadIdx.x] = send ? ws_ucount[t * SPLIT + threadIdx.x] : 0;
+    if (quant)
+        for (int j = threadIdx.x; j < N * SPLIT; j += blockDim.x)
+            s_am[j] = absmax_all[(int64_t)(j / SPLIT) * am_pitch + t * SPLIT + (j % SPLIT)];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int cap = (int)(cap_base[t + 1] - cap_base[t]);
+        int run = 0;
+        for (int ss = 0; ss < SPLIT; ++ss) {
+            int c = s_cnt[ss];
+            c = c < cap - run ? c : cap - run;  // overflow: the table's payload is truncated
+            c = c < 0 ? 0 : c;
+            if (ss == s) { s_pre = run; s_my = c; }
+            if (s == 0) reinterpret_cast<int32_t*>(payload)[t * SPLIT + ss] = c;
+            run += c;
+        }
+        if (quant) {  // rank scales, then Gloo's one-element all_reduce order
+            const float inv_n = (float)(1.0 / (double)N);
+            float acc = 0.0f;
+            for (int r = N - 1; r >= 0; --r) {
+                float am = 0.0f;
+                for (int ss = 0; ss < SPLIT; ++ss) am = fmaxf(am, s_am[r * SPLIT + ss]);
+                const float sr = sym_scale(am, bits);
+                acc = r == N - 1 ? sr : acc + sr;
+            }
+            const float sv = acc * inv_n;
+            s_sc = sv;
+            if (s == 0) s_avg[t] = sv;
+        }
+    }
+    __syncthreads();
+    const int cnt = s_my;
+    const int64_t src0 = ws_cap_base[k], dst0 = cap_base[t] + s_pre;
+    const bool qv = quant || (ranked && send);  // values are quantized
+    const float rr = quant ? 1.0f / s_sc : (qv ? 1.0f / tscale[t] : 0.0f);
+    const int lane = threadIdx.x % LPR;
+    constexpr int QU = 4;                 // entries in flight per lane group
+    constexpr int EPI = 512 / LPR;        // lane groups per workgroup
+    const int qb = ranked ? (send ? tb : 2) : bits;
+    const float qlo = -(float)(1 << (qb - 1)), qhi = (float)((1 << (qb - 1)) - 1);
+    for (int u0 = threadIdx.x / LPR; u0 < cnt; u0 += QU * EPI) {
+        float4 v[QU];
+        int32_t row[QU];
+#pragma unroll
+        for (int h = 0; h < QU; ++h) {  // QU entries' loads in flight
+            const int u = u0 + h * EPI;
+            if (u < cnt) {
+                v[h] = reinterpret_cast<const float4*>(ws_vals + (src0 + u) * D)[lane];
+                row[h] = ws_rows[src0 + u];
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < QU; ++h) {
+            const int u = u0 + h * EPI;
+            if (u >= cnt) continue;
+            const int64_t q = dst0 + u;  // dense payload entry
+            if (lane == 0) reinterpret_cast<int32_t*>(payload + pl.rows_off)[q] = row[h];
+            if (!qv) {
+                reinterpret_cast<float4*>(payload + pl.vals_off + q * D * 4)[lane] = v[h];
+                continue;
+            }
+            const float q0 = fake_quant(v[h].x, rr, qlo, qhi), q1 = fake_quant(v[h].y, rr, qlo, qhi);
+            const float q2 = fake_quant(v[h].z, rr, qlo, qhi), q3 = fake_quant(v[h].w, rr, qlo, qhi);
+            if (pl.elem == 1) {
+                uint32_t pk = ((uint32_t)(uint8_t)(int8_t)(int)q0) | ((uint32_t)(uint8_t)(int8_t)(int)q1 << 8) |
+                              ((uint32_t)(uint8_t)(int8_t)(int)q2 << 16) | ((uint32_t)(uint8_t)(int8_t)(int)q3 << 24);
+                reinterpret_cast<uint32_t*>(payload + pl.vals_off + q * D)[lane] = pk;
+            } else {
+                uint2 pk;
+                pk.x = ((uint32_t)(uint16_t)(int16_t)(int)q0) | ((uint32_t)(uint16_t)(int16_t)(int)q1 << 16);
+                pk.y = ((uint32_t)(uint16_t)(int16_t)(int)q2) | ((uint32_t)(uint16_t)(int16_t)(int)q3 << 16);
+                reinterpret_cast<uint2*>(payload + pl.vals_off + q * D * 2)[lane] = pk;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dqrm_grad_quant_pack_strided(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
+                                 const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
+                                 const float* absmax_all, int64_t absmax_pitch, int num_ranks, int grad_bits,
+                                 const int64_t* cap_base, int64_t cap_total, float* s_avg, void* payload,
+                                 void* stream) {
+    if (num_tables <= 0 || num_tables > dqrm_internal::kMaxTables || num_ranks <= 0 || num_ranks > 64)
+        return set_error(DQRM_E_INVALID, "%s: bad num_tables/num_ranks", "dqrm_grad_quant_pack");
+    if (!(grad_bits == 32 || (grad_bits >= 2 && grad_bits <= 16)))
+        return set_error(DQRM_E_INVALID, "%s: grad bits %d unsupported", "dqrm_grad_quant_pack", grad_bits);
+    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !cap_base || !payload ||
+        (grad_bits != 32 && (!absmax_all || !s_avg)))
+        return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_grad_quant_pack");
+    if (num_ranks > 1 && absmax_pitch < (int64_t)num_tables * SPLIT)
+        return set_error(DQRM_E_INVALID, "%s: absmax pitch %lld < %d", "dqrm_grad_quant_pack",
+                         (long long)absmax_pitch, num_tables * SPLIT);
+    if (((uintptr_t)payload) & 15)
+        return set_error(DQRM_E_INVALID, "%s: payload must be 16-B aligned", "dqrm_grad_quant_pack");
+    hipStream_t st = (hipStream_t)stream;
+    if (!dqrm_internal::env_qpack_legacy()) {  // (legacy: the one-workgroup-per-slot kernel, A/B)
+        QuantPackArgs q{num_tables, dim, ws_cap_base, ws_rows, ws_vals, ws_ucount, absmax_all, absmax_pitch,
+                        num_ranks, grad_bits, cap_base, cap_total, s_avg, (unsigned char*)payload};
+        DQRM_HIP_TRY(launch_quant_pack(q, st));
+        return DQRM_OK;
+    }
+    DISPATCH_LPR(dim, {
+        hipLaunchKernelGGL(k_quant_pack<LPR>, dim3(num_tables * SPLIT), dim3(512), 0, st,
+                           num_tables, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount, absmax_all,
+                           absmax_pitch, num_ranks, grad_bits, cap_base, cap_total, s_avg, (unsigned char*)payload,
+                           (const int32_t*)nullptr, (const float*)nullptr);
+    });
+    LAUNCH_CHECK();
+    return DQRM_OK;
+}
+
+int dqrm_grad_quant_pack(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
+                         const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
+                         const float* absmax_all, int num_ranks, int grad_bits, const int64_t* cap_base,
+                         int64_t cap_total, float* s_avg, void* payload, void* stream) {
+    return dqrm_grad_quant_pack_strided(num_tables, dim, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount,
+                                        absmax_all, (int64_t)num_tables * SPLIT, num_ranks, grad_bits, cap_base,
+                                        cap_total, s_avg, payload, stream);
+}
+
+int dqrm_grad_quant_pack_ranked(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
+                                const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
+                                const int32_t* table_bits, const float* table_scale, const int64_t* cap_base,
+                                int64_t cap_total, void* payload, void* stream) {
+    if (num_tables <= 0 || num_tables > dqrm_internal::kMaxTables)
+        return set_error(DQRM_E_INVALID, "%s: bad num_tables", "dqrm_grad_quant_pack_ranked");
+    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !table_bits || !table_scale || !cap_base || !payload)
+        return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_grad_quant_pack_ranked");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_LPR(dim, {
+        hipLaunchKernelGGL(k_quant_pack<LPR>, dim3(num_tables * SPLIT), dim3(512), 0, st,
+                           num_tables, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount,
+                           (const float*)nullptr, (int64_t)0, 1, 8, cap_base, cap_total, (float*)nullptr,
+                           (unsigned char*)payload, table_bits, table_scale);
+    });
+    LAUNCH_CHECK();
+    return DQRM_OK;
+}
+
+}  // extern "C"

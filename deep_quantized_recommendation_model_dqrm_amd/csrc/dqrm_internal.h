@@ -1,5 +1,6 @@
 // dqrm_internal.h — what the translation units of libdqrm share on the host (not part of the
-// C ABI; include/dqrm.h is): the error path, the validation one unit does for another, and the
+// C ABI; include/dqrm.h is): the error path, the environment switches and the validators
+// (dqrm_host.hip's), the dimension dispatch, the validation one unit does for another, and the
 // launch interface between units. A new unit includes this and defines no copy of any of it.
 #pragma once
 
@@ -13,7 +14,7 @@ namespace dqrm_internal {
 #define DQRM_HIDDEN __attribute__((visibility("hidden")))
 
 // The one error path: formats into the calling thread's dqrm_last_error() text and returns
-// `code` (dqrm_kernels.hip).
+// `code` (dqrm_host.hip).
 DQRM_HIDDEN __attribute__((format(printf, 2, 3))) int set_error(int code, const char* fmt, ...);
 
 #define DQRM_HIP_TRY(expr)                                                                                      \
@@ -22,8 +23,39 @@ DQRM_HIDDEN __attribute__((format(printf, 2, 3))) int set_error(int code, const 
         if (e_ != hipSuccess)                                                                                   \
             return dqrm_internal::set_error(DQRM_E_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
     } while (0)
+#define LAUNCH_CHECK() DQRM_HIP_TRY(hipGetLastError())
 
-// ---- The environment switches: one accessor each, all defined in one block of dqrm_kernels.hip,
+// Runs the statement with LPR = D / 4 (lanes per row, a float4 each) as a constant.
+#define DISPATCH_LPR(D, ...)                                  \
+    switch ((D) / 4) {                                        \
+        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;  \
+        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;  \
+        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;  \
+        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;  \
+        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
+        case 32: { constexpr int LPR = 32; __VA_ARGS__; } break; \
+        case 64: { constexpr int LPR = 64; __VA_ARGS__; } break; \
+        default: return dqrm_internal::set_error(DQRM_E_INVALID, "dqrm: unsupported dim %d", (int)(D)); \
+    }
+
+constexpr int kMaxTables = 256;  // tables of a dqrm_table_set or dqrm_rowwise_set
+
+// ---- The validators several units' exports share (dqrm_host.hip); `who`: the export the text names.
+// the table set: non-null, 1..kMaxTables tables, dim 4*2^k <= 256, every state pointer, W 16-B aligned
+DQRM_HIDDEN int check_set(const dqrm_table_set* s);
+// the batch: its three pointers, and at most 2^32 bags (DQRM_E_CAPACITY)
+DQRM_HIDDEN int check_batch(const dqrm_batch* batch, const char* who);
+// dy: non-null, 16-B aligned, strides % 4 == 0
+DQRM_HIDDEN int check_dy(const float* dy, int64_t dy_stride_t, int64_t dy_stride_b, const char* who);
+// repack_bits: 0, or 4 on a set with packed rows
+DQRM_HIDDEN int check_repack(const dqrm_table_set* set, int repack_bits, const char* who);
+// the coalesced-gradient slot workspace; rest_ok: what else the caller needs of it (s_avg, a total)
+DQRM_HIDDEN int check_slot_ws(const int64_t* ws_cap_base, const int32_t* ws_rows, const float* ws_vals,
+                              const int32_t* ws_ucount, const float* ws_absmax, const char* who, bool rest_ok = true);
+// workgroups of `threads` for work_items, at least 1 and at most max_blocks (grid-stride kernels)
+DQRM_HIDDEN int grid_for(int64_t work_items, int threads, int max_blocks = 2048);
+
+// ---- The environment switches: one accessor each, all defined in one block of dqrm_host.hip,
 // the only place of libdqrm that reads a DQRM_* variable ("Environment
 // switches", lists them for users). Every switch is an A/B or test handle on a choice DESIGN.md 8
 // measured; unset, each leaves the measured default. Unless said otherwise a switch is read once
@@ -202,50 +234,6 @@ void plan_sub_slots(const int64_t* num_rows_host, int T, LocalApplyArgs* la);
 // launches k_coalesce_p1 (dqrm_coalesce.hip); la != nullptr: the fused update as well
 // (hipErrorInvalidValue if !coalesce_apply_resident). Returns the HIP error of the launch.
 hipError_t launch_coalesce_pool1(const CoalesceArgs& a, const LocalApplyArgs* la, hipStream_t stream);
-
-// K5 quantize-pack of the N > 1 exchange (dqrm_exchange.hip): the rank's slot workspace ->
-// its wire payload, the table scales averaged over the all-gathered per-slot maxima
-// (dqrm_grad_quant_pack_strided's arguments, validated by the caller).
-struct QuantPackArgs {
-    int T;
-    int D;
-    const int64_t* ws_cap_base;  // [T*S+1]
-    const int32_t* ws_rows;
-    const float* ws_vals;
-    const int32_t* ws_ucount;
-    const float* absmax_all;     // [N][pitch], rank r's per-slot max|grad| at r*pitch + t*S + s
-    int64_t am_pitch;
-    int N;
-    int bits;                    // 2..16 quantized, 32 = FP32 values
-    const int64_t* cap_base;     // [T+1] payload capacity prefix
-    int64_t cap_total;
-    float* s_avg;                // [T]
-    unsigned char* payload;
-    uint32_t wt;                 // wt_stores() bits (WT_HAND: the payload values write-through)
-};
-hipError_t launch_quant_pack(const QuantPackArgs& a, hipStream_t stream);
-
-// The pre-summed per-lookup gradient (dqrm_lookup.hip, dqrm_emb_bwd_lookup_grad_presum):
-// one workgroup per table of at most kPresumMaxL lookups.
-constexpr int kPresumMaxL = DQRM_PRESUM_MAX_LOOKUPS;
-struct PresumArgs {
-    const int64_t* meta;
-    const float* scale;
-    uint32_t* err;
-    const int64_t* idx;
-    const int64_t* off;
-    const int64_t* idx_base;
-    const float* dy;
-    int64_t dst_t, dst_b;
-    int64_t B;
-    int64_t* rows;
-    float* vals;
-    int T;
-    int D;
-    int ste;
-    int pool1;
-};
-hipError_t launch_lookup_grad_presum(const PresumArgs& a, hipStream_t stream);
 
 // K6 with row ranges owned per workgroup (dqrm_apply.hip, DQRM_APPLY_RANGES): the gathered
 // payloads decoded, summed over ranks, applied, and the |W| hierarchy finalized in-launch.

@@ -1,15 +1,22 @@
-// dqrm_kernels.hip — CDNA4 (gfx950) kernels and the C ABI of libdqrm.
+// dqrm_kernels.hip — the embedding step of libdqrm on CDNA4 (gfx950): its kernels, launch plans
+// and exports.
 //
-// Hot path: DQRM's data-parallel QAT step for embedding tables
+// DQRM's data-parallel QAT step for embedding tables
 // (reference YangZhou08/Deep_Quantized_Recommendation_Model_DQRM @ 2024-10-24):
 //   fwd   QuantEmbeddingBagTwo.forward      quantization_supp/quant_modules_not_quantize_grad.py:317-398
 //   bwd   SymmetricQuantFunction.backward   quantization_supp/quant_utils.py:349-363
 //   sgd   torch.optim.SGD (sparse)          dlrm_s_pytorch_single_gpu.py:1736-1750,1943-1950
-//   dp    quantize_emb_grad / grad_update_parallel_comm / weight_update_parallel_comm
-//                                           sgd_quantized_gradients_parallel_comm.py:257-317,601-628,850-890
+//   dp    grad_update_parallel_comm / weight_update_parallel_comm
+//                                           sgd_quantized_gradients_parallel_comm.py:257-317,601-628
+//
+// Here: the forward (K3), the slot sort and coalesce (K4), the apply kernels (K6), the fused
+// backward and k_sgd_small, which share their device code and host plans. The stages that share
+// only validators with them have units of their own: dqrm_tables.hip (K0-K2), dqrm_exchange.hip
+// (K5), dqrm_lookup.hip, dqrm_rowwise.hip; the error path, environment switches and shared
+// validators are dqrm_host.hip's.
 //
 // Everything here is integer/byte/gather work: HBM- or latency-bound, no MFMA.
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see build.py). fp-contract must
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (_build.py). fp-contract must
 // stay off: the reference's `1/s*x + 0`, `(g*s)/s`, `W + (-lr*v)` are separately rounded;
 // the one fused multiply-add the reference does perform (torch CPU's sparse SGD axpy) is
 // written as an explicit fmaf.
@@ -17,7 +24,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdarg.h>
 #include <string.h>
 #include <math.h>
 #include <stdlib.h>
@@ -54,261 +60,16 @@ __device__ unsigned long long g_diag_clk[8192 * 16];
 #define DIAG_C(k) do { } while (0)
 #endif
 
-// ------------------------------------------------------------------------------------
-// error reporting (host)
-// ------------------------------------------------------------------------------------
-thread_local char g_last_error[512] = "";
-
-}  // namespace
-
-int dqrm_internal::set_error(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// ------------------------------------------------------------------------------------
-// The environment switches (host): every DQRM_* variable libdqrm reads is read here and nowhere
-// else; dqrm_internal.h documents each accessor (values, default, what it selects), and
-// INTEGRATION.md lists them all. Read once per process, on first use, unless said otherwise.
-// ------------------------------------------------------------------------------------
-static bool env_is(const char* e, const char* value) { return e && !strcmp(e, value); }
-static uint32_t env_u32(const char* e, uint32_t dflt) { return e ? (uint32_t)strtoul(e, nullptr, 10) : dflt; }
-
-// Unset or anything else: the default, y ("write-through stores of once-written
-// outputs": the hand-over buffers gained on the forced-collectives line only and moved no
-// WRITE_SIZE, the wide tables' W rows did not gain and are not in the code).
-uint32_t dqrm_internal::wt_stores(int dim) {
-    static const uint32_t v = [] {
-        const char* e = getenv("DQRM_WT_STORES");
-        if (env_is(e, "0")) return 0u;
-        if (env_is(e, "hand")) return WT_HAND;
-        if (env_is(e, "all")) return WT_Y | WT_HAND;
-        return WT_Y;
-    }();
-    return dim * (int)sizeof(float) >= 128 ? v : v & ~WT_Y;  // y rows of whole L2 lines only
-}
-int dqrm_internal::env_apply() {  // not cached here: apply_kernel_kind() holds the value
-    const char* e = getenv("DQRM_APPLY");
-    return env_is(e, "flat") ? DQRM_APPLY_FLAT : env_is(e, "slot") ? DQRM_APPLY_SLOT
-           : env_is(e, "ranges") ? DQRM_APPLY_RANGES : env_is(e, "merge") ? DQRM_APPLY_MERGE : DQRM_APPLY_AUTO;
-}
-int dqrm_internal::env_finalize() {
-    static const int v = [] {
-        const char* e = getenv("DQRM_FINALIZE");
-        return env_is(e, "launch") ? 1 : env_is(e, "inline") ? 2 : 0;
-    }();
-    return v;
-}
-bool dqrm_internal::env_fin_flagged() {
-    static const bool off = env_is(getenv("DQRM_FIN_FLAGGED"), "0");
-    return !off;
-}
-bool dqrm_internal::env_fused_fwd() {
-    static const bool off = env_is(getenv("DQRM_FUSED_FWD"), "0");
-    return !off;
-}
-bool dqrm_internal::env_fin_fwd() {
-    static const bool off = env_is(getenv("DQRM_FIN_FWD"), "0");
-    return !off;
-}
-bool dqrm_internal::env_local_fused() {
-    static const bool off = env_is(getenv("DQRM_LOCAL_FUSED"), "0");
-    return !off;
-}
-bool dqrm_internal::env_qpack_legacy() {
-    static const bool v = env_is(getenv("DQRM_QPACK"), "legacy");
-    return v;
-}
-int64_t dqrm_internal::env_merge_keys() {
-    static const int64_t v = [] {
-        const char* e = getenv("DQRM_MERGE_KEYS");
-        const long k = e ? atol(e) : 256;
-        return (int64_t)(k > 0 ? k : 256);
-    }();
-    return v;
-}
-int dqrm_internal::env_merge_diag() {
-    static const int v = [] {
-        const char* e = getenv("DQRM_MERGE_DIAG");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-int dqrm_internal::env_flat_dual() {  // read on every call: tests switch it inside one process
-    const char* e = getenv("DQRM_FLAT_DUAL");
-    return e ? atoi(e) : -1;
-}
-uint32_t dqrm_internal::env_gate_spin() {
-    static const uint32_t v = env_u32(getenv("DQRM_GATE_SPIN"), 1u << 20);
-    return v;
-}
-uint32_t dqrm_internal::env_stall_spin() {
-    static const uint32_t v = env_u32(getenv("DQRM_STALL_SPIN"), 1u << 20);
-    return v;
-}
-bool dqrm_internal::env_subslots() {
-    static const bool off = env_is(getenv("DQRM_SUBSLOTS"), "0");
-    return !off;
-}
-bool dqrm_internal::env_subslot_small_first() {
-    static const bool v = env_is(getenv("DQRM_SUBSLOT_ORDER"), "small");
-    return v;
-}
-bool dqrm_internal::env_table_groups_critical() {
-    static const bool v = env_is(getenv("DQRM_TABLE_GROUPS"), "critical");
-    return v;
-}
-
-namespace {
-
+using dqrm_internal::check_batch;
+using dqrm_internal::check_dy;
+using dqrm_internal::check_repack;
+using dqrm_internal::check_set;
+using dqrm_internal::check_slot_ws;
+using dqrm_internal::grid_for;
+using dqrm_internal::kMaxTables;
 using dqrm_internal::set_error;
 
-#define LAUNCH_CHECK() DQRM_HIP_TRY(hipGetLastError())
-
-constexpr int MAX_TABLES = 256;
 constexpr int DQRM_MAX_RANKS = 64;    // dqrm_apply_sparse_update: num_ranks <= 64
-
-
-// ------------------------------------------------------------------------------------
-// K0: synthetic init, U(-sqrt(1/n), sqrt(1/n)) per table (q_m_n_q_g.py:273-275 distribution)
-// ------------------------------------------------------------------------------------
-DQRM_INLINE uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__global__ void k_init_uniform(float* __restrict__ W, const int64_t* __restrict__ meta, int T,
-                               int D, int64_t total_rows, uint64_t seed) {
-    Meta m = make_meta(meta, T);
-    const int64_t n4 = total_rows * (D / 4);
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4;
-         q += (int64_t)gridDim.x * blockDim.x) {
-        int64_t row = q / (D / 4);
-        int t = find_table(m.row_base, T, row);
-        float bound = sqrtf(1.0f / (float)m.num_rows[t]);
-        uint64_t h0 = splitmix64(seed ^ ((uint64_t)q * 2ull));
-        uint64_t h1 = splitmix64(seed ^ ((uint64_t)q * 2ull + 1ull));
-        float4 v;
-        v.x = ((float)(uint32_t)(h0 >> 40) * (1.0f / 16777216.0f)) * 2.0f - 1.0f;
-        v.y = ((float)(uint32_t)((h0 >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f)) * 2.0f - 1.0f;
-        v.z = ((float)(uint32_t)(h1 >> 40) * (1.0f / 16777216.0f)) * 2.0f - 1.0f;
-        v.w = ((float)(uint32_t)((h1 >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f)) * 2.0f - 1.0f;
-        v.x *= bound; v.y *= bound; v.z *= bound; v.w *= bound;
-        reinterpret_cast<float4*>(W)[q] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// K1: absolute-max hierarchy  rowmax -> blkmax -> sblkmax -> tmax
-// (exact replacement of the full-table min/max, quant_utils.py:177-178)
-// ------------------------------------------------------------------------------------
-template <int LPR>  // lanes per row = D/4
-__global__ void k_rowmax_all(const float* __restrict__ W, float* __restrict__ rowmax,
-                             int64_t total_rows) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ngrp = (int64_t)gridDim.x * blockDim.x / LPR;
-    const int lane = threadIdx.x % LPR;
-    for (int64_t row = gid / LPR; row < total_rows; row += ngrp) {
-        float4 v = reinterpret_cast<const float4*>(W + row * (LPR * 4))[lane];
-        float m = group_max<LPR>(abs_max4(v));
-        if (lane == 0) rowmax[row] = m;
-    }
-}
-
-// one wave per output: out[ob_t + j] = max(in[ib_t + j*256 .. min(+256, nin_t)])
-// level 1: in = rowmax (ib = row_base, nin = num_rows), out = blkmax (ob = blk_base)
-// level 2: in = blkmax (ib = blk_base, nin = nblk),     out = sblkmax (ob = sblk_base)
-__global__ void k_level_max(const float* __restrict__ in, float* __restrict__ out,
-                            const int64_t* __restrict__ meta, int T, int level,
-                            int64_t total_out) {
-    Meta m = make_meta(meta, T);
-    const int lane = threadIdx.x % WAVE;
-    const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
-    const int64_t nw = (int64_t)gridDim.x * blockDim.x / WAVE;
-    const int64_t* ob = level == 1 ? m.blk_base : m.sblk_base;
-    for (int64_t o = wid; o < total_out; o += nw) {
-        int t = find_table(ob, T, o);
-        int64_t j = o - ob[t];
-        int64_t ib = level == 1 ? m.row_base[t] : m.blk_base[t];
-        int64_t nin = level == 1 ? m.num_rows[t] : ceil_div(m.num_rows[t], BLK);
-        int64_t s0 = j * 256, s1 = s0 + 256 < nin ? s0 + 256 : nin;
-        float v = 0.0f;
-        for (int64_t k = s0 + lane; k < s1; k += WAVE) v = fmaxf(v, in[ib + k]);
-        v = wave_max(v);
-        if (lane == 0) out[o] = v;
-    }
-}
-
-// one workgroup per table: tmax[t] = max(sblkmax of t)
-__global__ void k_table_max(const float* __restrict__ sblkmax, float* __restrict__ tmax,
-                            const int64_t* __restrict__ meta, int T) {
-    Meta m = make_meta(meta, T);
-    __shared__ float red[16];
-    const int t = blockIdx.x;
-    const int64_t ns = ceil_div(ceil_div(m.num_rows[t], BLK), SBLK_BLOCKS);
-    float v = 0.0f;
-    for (int64_t k = threadIdx.x; k < ns; k += blockDim.x) v = fmaxf(v, sblkmax[m.sblk_base[t] + k]);
-    v = wave_max(v);
-    if ((threadIdx.x % WAVE) == 0) red[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float r = 0.0f;
-        for (int w = 0; w < (int)(blockDim.x / WAVE); ++w) r = fmaxf(r, red[w]);
-        tmax[t] = r;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// K2: periodic scale refresh + conditional INT4 repack
-// ------------------------------------------------------------------------------------
-__global__ void k_refresh_scale(const float* __restrict__ tmax, float* __restrict__ scale,
-                                float* __restrict__ pscale, uint32_t* __restrict__ tflags,
-                                int T, int bits, int has_packed) {
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    float s = sym_scale(tmax[t], bits);
-    scale[t] = s;
-    uint32_t need = 0;
-    if (has_packed) {
-        float ps = pscale[t];
-        need = !(ps == s);  // NaN pscale (never packed) -> repack
-        pscale[t] = s;
-    }
-    tflags[t] = need;
-}
-
-
-template <int LPR>
-DQRM_INLINE void pack_row_int4(const float4 w, uint8_t* __restrict__ packed, int64_t grow,
-                               int lane, float r) {
-    pack4_row(w, packed + grow * (LPR * 2), lane, r);
-}
-
-template <int LPR>
-__global__ void k_repack_flagged(const float* __restrict__ W, uint8_t* __restrict__ packed,
-                                 const float* __restrict__ scale,
-                                 const uint32_t* __restrict__ tflags,
-                                 const int64_t* __restrict__ meta, int T, int64_t total_rows) {
-    Meta m = make_meta(meta, T);
-    const int lane = threadIdx.x % LPR;
-    const int64_t ngrp = (int64_t)gridDim.x * blockDim.x / LPR;
-    const int64_t g0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPR;
-    for (int t = 0; t < T; ++t) {
-        if (!tflags[t]) continue;  // scale unchanged since the last pack: rows still exact
-        const float r = 1.0f / scale[t];
-        const int64_t r0 = m.row_base[t], r1 = r0 + m.num_rows[t];
-        for (int64_t row = r0 + g0; row < r1; row += ngrp) {
-            float4 w = reinterpret_cast<const float4*>(W + row * (LPR * 4))[lane];
-            pack_row_int4<LPR>(w, packed, row, lane, r);
-        }
-    }
-    (void)total_rows;
-}
 
 // ------------------------------------------------------------------------------------
 // K3: fused multi-table fake-quant EmbeddingBag forward
@@ -1480,136 +1241,6 @@ struct DimSplit {
 
 DQRM_INLINE bool narrow_table(int64_t nrows) { return nrows <= BLK; }
 
-// ------------------------------------------------------------------------------------
-// K5: scale average + quantize-pack (slot workspace -> dense wire payload)
-// ------------------------------------------------------------------------------------
-// (the wire payload layout, PayloadLayout / payload_layout: dqrm_device.h)
-
-// rank r's local scale from its slots' max |grad| (quant_utils.py:141-194 on the coalesced
-// values), then dist.all_reduce(SUM) + mul_(1./N) (s_q_g_p_c.py:861-866). Gloo's allreduce
-// of a one-element tensor accumulates in descending rank order
-// (((s_{N-1} + s_{N-2}) + ...) + s_0) — measured for N = 2..8 with torch 2.10's Gloo;
-// every rank evaluates the same order on the all-gathered values, so the average is
-// bit-identical across ranks and equal to the reference's.
-DQRM_INLINE float rank_scale(const float* absmax_all, int T, int r, int t, int bits) {
-    float a = 0.0f;
-    for (int s = 0; s < SPLIT; ++s) a = fmaxf(a, absmax_all[((int64_t)r * T + t) * SPLIT + s]);
-    return sym_scale(a, bits);
-}
-
-DQRM_INLINE float average_scale(const float* absmax_all, int T, int N, int t, int bits) {
-    const float inv_n = (float)(1.0 / (double)N);
-    float acc = rank_scale(absmax_all, T, N - 1, t, bits);
-    for (int r = N - 2; r >= 0; --r) acc = acc + rank_scale(absmax_all, T, r, t, bits);
-    return acc * inv_n;
-}
-
-// One workgroup per (table, slot): the table's 8 slot counts are clamped in slot order
-// against the table's payload capacity (overflow truncates the table), the N ranks'
-// per-slot max|grad| are staged in LDS and averaged in Gloo's order, then LPR lanes per
-// entry quantize and store the slot's entries at their dense payload position. Workgroup
-// (t, 0) also writes the table's header counts and s_avg[t].
-template <int LPR>
-__global__ void __launch_bounds__(512) k_quant_pack(int T, const int64_t* __restrict__ ws_cap_base,
-                                                    int64_t ws_cap_total, const int32_t* __restrict__ ws_rows,
-                                                    const float* __restrict__ ws_vals,
-                                                    const int32_t* __restrict__ ws_ucount,
-                                                    const float* __restrict__ absmax_all, int64_t am_pitch,
-                                                    int N, int bits,
-                                                    const int64_t* __restrict__ cap_base, int64_t cap_total,
-                                                    float* __restrict__ s_avg, unsigned char* __restrict__ payload,
-                                                    const int32_t* __restrict__ tbits,
-                                                    const float* __restrict__ tscale) {
-    __shared__ int s_cnt[SPLIT];
-    __shared__ float s_am[64 * SPLIT];
-    __shared__ int s_pre, s_my;
-    __shared__ float s_sc;
-    (void)ws_cap_total;
-    const int k = blockIdx.x, t = k / SPLIT, s = k % SPLIT;
-    const int D = LPR * 4;
-    const PayloadLayout pl = payload_layout(T, cap_total, D, bits);
-    // ranking range (tbits != NULL): per-table bit width and scale; 0 / 32-bit tables send
-    // nothing (grad_update_parallel_comm skips them, s_q_g_p_c.py:280-289)
-    const int tb = tbits ? tbits[t] : bits;
-    const bool ranked = tbits != nullptr;
-    const bool send = !ranked || (tb >= 2 && tb <= 8);
-    const bool quant = !ranked && bits >= 2 && bits <= 16;
-    if (threadIdx.x < SPLIT) s_cnt[threadIdx.x] = send ? ws_ucount[t * SPLIT + threadIdx.x] : 0;
-    if (quant)
-        for (int j = threadIdx.x; j < N * SPLIT; j += blockDim.x)
-            s_am[j] = absmax_all[(int64_t)(j / SPLIT) * am_pitch + t * SPLIT + (j % SPLIT)];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int cap = (int)(cap_base[t + 1] - cap_base[t]);
-        int run = 0;
-        for (int ss = 0; ss < SPLIT; ++ss) {
-            int c = s_cnt[ss];
-            c = c < cap - run ? c : cap - run;  // overflow: the table's payload is truncated
-            c = c < 0 ? 0 : c;
-            if (ss == s) { s_pre = run; s_my = c; }
-            if (s == 0) reinterpret_cast<int32_t*>(payload)[t * SPLIT + ss] = c;
-            run += c;
-        }
-        if (quant) {  // rank scales, then Gloo's one-element all_reduce order
-            const float inv_n = (float)(1.0 / (double)N);
-            float acc = 0.0f;
-            for (int r = N - 1; r >= 0; --r) {
-                float am = 0.0f;
-                for (int ss = 0; ss < SPLIT; ++ss) am = fmaxf(am, s_am[r * SPLIT + ss]);
-                const float sr = sym_scale(am, bits);
-                acc = r == N - 1 ? sr : acc + sr;
-            }
-            const float sv = acc * inv_n;
-            s_sc = sv;
-            if (s == 0) s_avg[t] = sv;
-        }
-    }
-    __syncthreads();
-    const int cnt = s_my;
-    const int64_t src0 = ws_cap_base[k], dst0 = cap_base[t] + s_pre;
-    const bool qv = quant || (ranked && send);  // values are quantized
-    const float rr = quant ? 1.0f / s_sc : (qv ? 1.0f / tscale[t] : 0.0f);
-    const int lane = threadIdx.x % LPR;
-    constexpr int QU = 4;                 // entries in flight per lane group
-    constexpr int EPI = 512 / LPR;        // lane groups per workgroup
-    const int qb = ranked ? (send ? tb : 2) : bits;
-    const float qlo = -(float)(1 << (qb - 1)), qhi = (float)((1 << (qb - 1)) - 1);
-    for (int u0 = threadIdx.x / LPR; u0 < cnt; u0 += QU * EPI) {
-        float4 v[QU];
-        int32_t row[QU];
-#pragma unroll
-        for (int h = 0; h < QU; ++h) {  // QU entries' loads in flight
-            const int u = u0 + h * EPI;
-            if (u < cnt) {
-                v[h] = reinterpret_cast<const float4*>(ws_vals + (src0 + u) * D)[lane];
-                row[h] = ws_rows[src0 + u];
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < QU; ++h) {
-            const int u = u0 + h * EPI;
-            if (u >= cnt) continue;
-            const int64_t q = dst0 + u;  // dense payload entry
-            if (lane == 0) reinterpret_cast<int32_t*>(payload + pl.rows_off)[q] = row[h];
-            if (!qv) {
-                reinterpret_cast<float4*>(payload + pl.vals_off + q * D * 4)[lane] = v[h];
-                continue;
-            }
-            const float q0 = fake_quant(v[h].x, rr, qlo, qhi), q1 = fake_quant(v[h].y, rr, qlo, qhi);
-            const float q2 = fake_quant(v[h].z, rr, qlo, qhi), q3 = fake_quant(v[h].w, rr, qlo, qhi);
-            if (pl.elem == 1) {
-                uint32_t pk = ((uint32_t)(uint8_t)(int8_t)(int)q0) | ((uint32_t)(uint8_t)(int8_t)(int)q1 << 8) |
-                              ((uint32_t)(uint8_t)(int8_t)(int)q2 << 16) | ((uint32_t)(uint8_t)(int8_t)(int)q3 << 24);
-                reinterpret_cast<uint32_t*>(payload + pl.vals_off + q * D)[lane] = pk;
-            } else {
-                uint2 pk;
-                pk.x = ((uint32_t)(uint16_t)(int16_t)(int)q0) | ((uint32_t)(uint16_t)(int16_t)(int)q1 << 16);
-                pk.y = ((uint32_t)(uint16_t)(int16_t)(int)q2) | ((uint32_t)(uint16_t)(int16_t)(int)q3 << 16);
-                reinterpret_cast<uint2*>(payload + pl.vals_off + q * D * 2)[lane] = pk;
-            }
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------
 // K6: decode N payloads, union rows, sum, dequantize, SGD update + maintenance.
@@ -3901,145 +3532,6 @@ __global__ void __launch_bounds__(SG_TPB) k_sgd_small(FArgs a) {
     DIAG_W(5);
 }
 
-// ------------------------------------------------------------------------------------
-// Row-wise PTQ formats of the reference's inference path:
-//   prepack   torch.ops.quantized.embedding_bag_{4bit,byte}_prepack
-//             (DLRM_Net.quantize_embedding, dlrm_s_pytorch_single_gpu_documentingp.py:689-704)
-//   gather    torch.ops.quantized.embedding_bag_{4bit,byte}_rowwise_offsets, mode sum
-//             (DLRM_Net.apply_emb, dlrm_s_pytorch_single_gpu_documentingp.py:648-663)
-// Row layout (FBGEMM fused row-wise): 4-bit: D/2 nibble bytes (element 2j in the low
-// nibble), fp16 scale, fp16 bias; 8-bit: D bytes, f32 scale, f32 bias. A row's scale and
-// bias are read once per lookup next to its payload; G = D/8 lanes per row, 8 dims per lane.
-// ------------------------------------------------------------------------------------
-__host__ __device__ inline int rowwise_row_bytes(int bits, int D) { return bits == 4 ? D / 2 + 4 : D + 8; }
-
-template <int G>
-DQRM_INLINE float group_min(float v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-template <int G>
-DQRM_INLINE float group_fmax(float v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
-template <int BITS, int G>
-__global__ void __launch_bounds__(256) k_rowwise_prepack(const float* __restrict__ W, int64_t n,
-                                                         uint8_t* __restrict__ out) {
-    constexpr int D = G * 8;
-    constexpr int RB = BITS == 4 ? D / 2 + 4 : D + 8;
-    const int lane = threadIdx.x % G;
-    const int64_t rows_per_pass = (int64_t)gridDim.x * (256 / G);
-    for (int64_t r = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G; r < n; r += rows_per_pass) {
-        const float4* src = reinterpret_cast<const float4*>(W + r * D) + lane * 2;
-        const float4 a = src[0], b = src[1];
-        float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        float mn = x[0], mx = x[0];
-#pragma unroll
-        for (int j = 1; j < 8; ++j) { mn = fminf(mn, x[j]); mx = fmaxf(mx, x[j]); }
-        mn = group_min<G>(mn);
-        mx = group_fmax<G>(mx);
-        uint8_t* orow = out + r * RB;
-        if (BITS == 4) {  // FloatOrHalfToFusedNBitRowwiseQuantizedSBHalf, bit_rate 4
-            const _Float16 mn16 = (_Float16)mn;  // round-to-nearest-even
-            const float mnh = (float)mn16;
-            const float range = mx - mnh;
-            const float scale = range == 0.0f ? 1.0f : range / 15.0f;
-            _Float16 s16 = (_Float16)scale;
-            const float sh = (float)s16;
-            float inv = sh == 0.0f ? 1.0f : 1.0f / sh;
-            if (sh == 0.0f || isinf(inv)) { s16 = (_Float16)1.0f; inv = 1.0f; }
-            uint32_t word = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float q = fminf(fmaxf(rintf((x[j] - mnh) * inv), 0.0f), 15.0f);
-                word |= (uint32_t)q << (4 * j);
-            }
-            reinterpret_cast<uint32_t*>(orow)[lane] = word;
-            if (lane == 0)
-                reinterpret_cast<uint32_t*>(orow + D / 2)[0] =
-                    (uint32_t)__builtin_bit_cast(uint16_t, s16) | ((uint32_t)__builtin_bit_cast(uint16_t, mn16) << 16);
-        } else {          // FloatToFused8BitRowwiseQuantizedSBFloat
-            const float range = mx - mn;
-            const float scale = range / 255.0f;
-            const float inv = 255.0f / (range + 1e-8f);
-            uint2 words = make_uint2(0u, 0u);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float q = fminf(fmaxf(rintf((x[j] - mn) * inv), 0.0f), 255.0f);
-                if (j < 4) words.x |= (uint32_t)q << (8 * j); else words.y |= (uint32_t)q << (8 * (j - 4));
-            }
-            reinterpret_cast<uint2*>(orow)[lane] = words;
-            if (lane == 0) reinterpret_cast<uint2*>(orow + D)[0] = make_uint2(__float_as_uint(scale), __float_as_uint(mn));
-        }
-    }
-}
-
-// EmbeddingSpMDM(NBit) reference semantics, mode sum: per lookup, in bag order,
-//   acc = fma(scale * w, q, acc + bias * w)     (w = per-sample weight, omitted when null)
-template <int BITS, int G>
-__global__ void __launch_bounds__(256) k_rowwise_bag(const uint8_t* __restrict__ packed, int64_t n,
-                                                     const int64_t* __restrict__ idx, int64_t L,
-                                                     const int64_t* __restrict__ off, int64_t B,
-                                                     const float* __restrict__ psw, int last_offset,
-                                                     float* __restrict__ out, uint32_t* __restrict__ err) {
-    constexpr int D = G * 8;
-    constexpr int RB = BITS == 4 ? D / 2 + 4 : D + 8;
-    const int lane = threadIdx.x % G;
-    const int64_t bags_per_pass = (int64_t)gridDim.x * (256 / G);
-    for (int64_t b = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G; b < B; b += bags_per_pass) {
-        int64_t s0 = off[b], s1 = (b + 1 < B || last_offset) ? off[b + 1] : L;
-        if (s0 < 0 || s1 > L || s1 < s0) {
-            if (lane == 0) flag_error(err, DQRM_ERRF_OFFSET);
-            s0 = s0 < 0 ? 0 : (s0 > L ? L : s0);
-            s1 = s1 < s0 ? s0 : (s1 > L ? L : s1);
-        }
-        float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
-        for (int64_t i = s0; i < s1; ++i) {
-            const int64_t r = idx[i];
-            if (r < 0 || r >= n) {
-                if (lane == 0) flag_error(err, DQRM_ERRF_INDEX);
-                continue;
-            }
-            const uint8_t* row = packed + r * RB;
-            float sc, bi;
-            uint32_t w0, w1 = 0;
-            if (BITS == 4) {
-                const uint32_t sb = *reinterpret_cast<const uint32_t*>(row + D / 2);
-                sc = (float)__builtin_bit_cast(_Float16, (uint16_t)(sb & 0xFFFFu));
-                bi = (float)__builtin_bit_cast(_Float16, (uint16_t)(sb >> 16));
-                w0 = reinterpret_cast<const uint32_t*>(row)[lane];
-            } else {
-                const uint2 sb = *reinterpret_cast<const uint2*>(row + D);
-                sc = __uint_as_float(sb.x);
-                bi = __uint_as_float(sb.y);
-                const uint2 w = reinterpret_cast<const uint2*>(row)[lane];
-                w0 = w.x;
-                w1 = w.y;
-            }
-            if (psw) {
-                const float wt = psw[i];
-                sc = sc * wt;
-                bi = bi * wt;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float q = BITS == 4 ? (float)((w0 >> (4 * j)) & 15u)
-                                          : (float)(((j < 4 ? w0 : w1) >> (8 * (j & 3))) & 255u);
-                acc[j] = fmaf(sc, q, acc[j] + bi);
-            }
-        }
-        float4* o = reinterpret_cast<float4*>(out + b * D) + lane * 2;
-        o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    }
-}
 
 // ------------------------------------------------------------------------------------
 // Rows rewritten outside libdqrm (torch.optim.SGD stepping on the grad_mode="sparse" COO):
@@ -4128,121 +3620,6 @@ __global__ void __launch_bounds__(256) k_fwd_after_update(FwdArgs a, float* __re
     emb_fwd_table<LPR, 4, true>(a, 0, 0, 1);
 }
 
-// ------------------------------------------------------------------------------------
-// Per-lookup (uncoalesced) sparse gradient, the form nn.EmbeddingBag(sparse=True) hands to
-// autograd (embedding_bag_backward's sparse branch: indices = the input indices, values =
-// the bag's gradient row once per lookup, in lookup order): lookup j of table t gets
-// rows[j] = row_base[t] + idx[j] and vals[j] = (dy[t, bag(j)] * s_t) / s_t (STE,
-// quant_utils.py:349-363). One lane group per bag, its dy row loaded once and stored for
-// each of its lookups (coalesced float4 stores), grid (bag chunks, tables).
-// ------------------------------------------------------------------------------------
-struct LgArgs {
-    const int64_t* meta;
-    const float* scale;
-    uint32_t* err;
-    const int64_t* idx;
-    const int64_t* off;
-    const int64_t* idx_base;
-    const float* dy;
-    int64_t dst_t, dst_b;
-    int64_t B;
-    int64_t* rows;
-    float* vals;
-    int T;
-    int ste;
-    int pool1;
-};
-
-template <int LPR>
-__global__ void __launch_bounds__(256) k_lookup_grad(LgArgs a) {
-    const int t = blockIdx.y;
-    constexpr int G = 256 / LPR;
-    const int lane = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    const int D = LPR * 4;
-    const float s = a.scale[t];
-    const int64_t rowbase = a.meta[t], nrows = a.meta[a.T + t];
-    // Criteo form: table t's lookups are idx[t*B, (t+1)*B) -- no idx_base round trip in front of the index loads
-    const int64_t ibase = a.pool1 ? (int64_t)t * a.B : a.idx_base[t];
-    const int64_t L = a.pool1 ? a.B : a.idx_base[t + 1] - ibase;
-    const int64_t B = a.B;
-    const int64_t* __restrict__ off = a.off + (int64_t)t * B;
-    const bool p1 = a.pool1 && L == B;
-    for (int64_t b = (int64_t)blockIdx.x * G + grp; b < B; b += (int64_t)gridDim.x * G) {
-        int64_t s0 = p1 ? b : off[b];
-        int64_t s1 = p1 ? b + 1 : ((b + 1 < B) ? off[b + 1] : L);
-        if (s0 < 0 || s1 > L || s1 < s0 || (b == 0 && s0 != 0)) {  // nn.EmbeddingBag needs off[0] == 0
-            if (lane == 0) flag_error(a.err, DQRM_ERRF_OFFSET);
-            s0 = s0 < 0 ? 0 : (s0 > L ? L : s0);
-            s1 = s1 < s0 ? s0 : (s1 > L ? L : s1);
-            if (b == 0)  // lookups before the first bag: zero rows on the table's row 0, never garbage
-                for (int64_t j = 0; j < s0; ++j) {
-                    if (lane == 0) a.rows[ibase + j] = rowbase;
-                    reinterpret_cast<float4*>(a.vals + (ibase + j) * D)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-        }
-        if (s1 == s0) continue;
-        float4 g = reinterpret_cast<const float4*>(a.dy + (int64_t)t * a.dst_t + b * a.dst_b)[lane];
-        if (a.ste) { g.x = (g.x * s) / s; g.y = (g.y * s) / s; g.z = (g.z * s) / s; g.w = (g.w * s) / s; }
-        for (int64_t j = s0; j < s1; ++j) {
-            int64_t r = a.idx[ibase + j];
-            float4 v = g;
-            if (r < 0 || r >= nrows) {  // flagged; the entry becomes a zero row on the table's row 0
-                if (lane == 0) flag_error(a.err, DQRM_ERRF_INDEX);
-                r = 0;
-                v = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            if (lane == 0) a.rows[ibase + j] = rowbase + r;
-            reinterpret_cast<float4*>(a.vals + (ibase + j) * D)[lane] = v;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// host helpers
-// ------------------------------------------------------------------------------------
-int check_set(const dqrm_table_set* s) {
-    if (!s) return set_error(DQRM_E_INVALID, "dqrm: null table set");
-    if (s->num_tables <= 0 || s->num_tables > MAX_TABLES)
-        return set_error(DQRM_E_INVALID, "dqrm: num_tables out of range (%d)", s->num_tables);
-    const int D = s->dim;
-    if (D < 4 || D > 256 || (D & 3) || ((D / 4) & (D / 4 - 1)))
-        return set_error(DQRM_E_INVALID, "dqrm: dim must be 4*2^k <= 256 (got %d)", D);
-    if (!s->W || !s->rowmax || !s->blkmax || !s->sblkmax || !s->tmax || !s->scale || !s->pscale ||
-        !s->meta || !s->err || !s->tflags || !s->sdirty || !s->bdirty || !s->sync)
-        return set_error(DQRM_E_INVALID, "dqrm: null state pointer");
-    if (((uintptr_t)s->W) & 15)
-        return set_error(DQRM_E_INVALID, "dqrm: W must be 16-byte aligned");
-    return DQRM_OK;
-}
-
-// The checks several exports share; `who` is the export name the text reports.
-int check_batch(const dqrm_batch* batch, const char* who) {
-    if (!batch || !batch->idx || !batch->off || !batch->idx_base)
-        return set_error(DQRM_E_INVALID, "%s: null batch pointer", who);
-    if (batch->num_bags > 0xFFFFFFFFll)
-        return set_error(DQRM_E_CAPACITY, "%s: more than 2^32 bags", who);
-    return DQRM_OK;
-}
-
-int check_dy(const float* dy, int64_t dy_stride_t, int64_t dy_stride_b, const char* who) {
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return set_error(DQRM_E_INVALID, "%s: dy must be 16-B aligned with strides %% 4 == 0", who);
-    return DQRM_OK;
-}
-
-int check_repack(const dqrm_table_set* set, int repack_bits, const char* who) {
-    if (repack_bits && (repack_bits != 4 || !set->packed))
-        return set_error(DQRM_E_INVALID, "%s: repack needs packed rows and bits == 4 (got %d)", who, repack_bits);
-    return DQRM_OK;
-}
-
-// the coalesced-gradient slot workspace; rest_ok: what else the caller needs of it (s_avg, a total)
-int check_slot_ws(const int64_t* ws_cap_base, const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
-                  const float* ws_absmax, const char* who, bool rest_ok = true) {
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !ws_absmax || !rest_ok || (((uintptr_t)ws_vals) & 15))
-        return set_error(DQRM_E_INVALID, "%s: null/unaligned workspace", who);
-    return DQRM_OK;
-}
 
 // the forward's argument checks (every entry point that runs a forward)
 int check_fwd(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags, const float* out,
@@ -4292,24 +3669,6 @@ int launch_finalize(const dqrm_table_set* set, hipStream_t st, bool tracked = fa
     return DQRM_OK;
 }
 
-int grid_for(int64_t work_items, int threads, int max_blocks = 2048) {
-    int64_t b = (work_items + threads - 1) / threads;
-    if (b < 1) b = 1;
-    if (b > max_blocks) b = max_blocks;
-    return (int)b;
-}
-
-#define DISPATCH_LPR(D, ...)                                  \
-    switch ((D) / 4) {                                        \
-        case 1: { constexpr int LPR = 1; __VA_ARGS__; } break;  \
-        case 2: { constexpr int LPR = 2; __VA_ARGS__; } break;  \
-        case 4: { constexpr int LPR = 4; __VA_ARGS__; } break;  \
-        case 8: { constexpr int LPR = 8; __VA_ARGS__; } break;  \
-        case 16: { constexpr int LPR = 16; __VA_ARGS__; } break; \
-        case 32: { constexpr int LPR = 32; __VA_ARGS__; } break; \
-        case 64: { constexpr int LPR = 64; __VA_ARGS__; } break; \
-        default: return set_error(DQRM_E_INVALID, "dqrm: unsupported dim %d", (int)(D)); \
-    }
 
 constexpr int LDS_PER_CU = 160 * 1024;  // gfx950: static + dynamic LDS of one workgroup
 
@@ -4926,8 +4285,6 @@ int dqrm_diag_clock_read(unsigned long long* host, int n) {
 }
 #endif
 
-const char* dqrm_last_error(void) { return g_last_error; }
-
 int dqrm_set_coalesce_kernel(int kind) {
     if (kind != DQRM_COALESCE_AUTO && kind != DQRM_COALESCE_GENERAL)
         return set_error(DQRM_E_INVALID, "dqrm_set_coalesce_kernel: unknown kind %d", kind);
@@ -4943,66 +4300,6 @@ int dqrm_set_apply_kernel(int kind) {
     return prev;
 }
 
-int dqrm_abi_version(void) { return DQRM_ABI_VERSION; }
-
-int dqrm_init_uniform(const dqrm_table_set* set, uint64_t seed, void* stream) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n4 = set->total_rows * (set->dim / 4);
-    hipLaunchKernelGGL(k_init_uniform, dim3(grid_for(n4, 256, 8192)), dim3(256), 0, st, set->W,
-                       set->meta, set->num_tables, set->dim, set->total_rows, seed);
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-int dqrm_refresh_absmax(const dqrm_table_set* set, void* stream) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int D = set->dim;
-    DISPATCH_LPR(D, {
-        hipLaunchKernelGGL(k_rowmax_all<LPR>, dim3(grid_for(set->total_rows * LPR, 256, 8192)), dim3(256), 0,
-                           st, set->W, set->rowmax, set->total_rows);
-    });
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_level_max, dim3(grid_for(set->total_blocks * WAVE, 256, 8192)), dim3(256), 0, st,
-                       set->rowmax, set->blkmax, set->meta, set->num_tables, 1, set->total_blocks);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_level_max, dim3(grid_for(set->total_sblocks * WAVE, 256, 8192)), dim3(256), 0, st,
-                       set->blkmax, set->sblkmax, set->meta, set->num_tables, 2, set->total_sblocks);
-    LAUNCH_CHECK();
-    DQRM_HIP_TRY(hipMemsetAsync(set->sdirty, 0, (size_t)set->total_sblocks, st));
-    DQRM_HIP_TRY(hipMemsetAsync(set->bdirty, 0, (size_t)set->total_blocks, st));
-    DQRM_HIP_TRY(hipMemsetAsync(set->sync, 0, (size_t)set->num_tables * DQRM_SYNC_STRIDE * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_table_max, dim3(set->num_tables), dim3(256), 0, st, set->sblkmax, set->tmax,
-                       set->meta, set->num_tables);
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-int dqrm_refresh_scale_and_pack(const dqrm_table_set* set, int bits, void* stream) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    if (bits < 2 || bits > 16) return set_error(DQRM_E_INVALID, "%s: bits %d unsupported", "refresh", bits);
-    if (set->packed && bits != 4)
-        return set_error(DQRM_E_INVALID, "%s: packed rows need bits == 4 (got %d)", "refresh", bits);
-    hipStream_t st = (hipStream_t)stream;
-    const int T = set->num_tables;
-    hipLaunchKernelGGL(k_refresh_scale, dim3((T + 255) / 256), dim3(256), 0, st, set->tmax, set->scale,
-                       set->pscale, set->tflags, T, bits, set->packed != nullptr);
-    LAUNCH_CHECK();
-    if (set->packed) {
-        const int D = set->dim;
-        DISPATCH_LPR(D, {
-            hipLaunchKernelGGL(k_repack_flagged<LPR>, dim3(grid_for(set->total_rows * LPR, 256, 8192)),
-                               dim3(256), 0, st, set->W, set->packed, set->scale, set->tflags, set->meta,
-                               T, set->total_rows);
-        });
-        LAUNCH_CHECK();
-    }
-    return DQRM_OK;
-}
 
 int dqrm_emb_fwd(const dqrm_table_set* set, const dqrm_batch* batch, int bits, uint32_t flags,
                  float* out, int64_t out_stride_t, int64_t out_stride_b, void* stream) {
@@ -5038,7 +4335,7 @@ int dqrm_emb_fwd_after_update(const dqrm_table_set* set, const dqrm_batch* batch
 }
 
 size_t dqrm_bwd_workspace_bytes(int num_tables, int64_t max_lookups) {
-    if (num_tables <= 0 || num_tables > MAX_TABLES || max_lookups < 0) return 0;
+    if (num_tables <= 0 || num_tables > kMaxTables || max_lookups < 0) return 0;
     return (size_t)fused_ws_layout(nullptr, num_tables, max_lookups > 0 ? max_lookups : 1, nullptr);
 }
 
@@ -5104,31 +4401,6 @@ int dqrm_rows_changed(const dqrm_table_set* set, const int64_t* rows, int64_t n,
     return fin ? DQRM_OK : launch_finalize(set, st, false);
 }
 
-int dqrm_emb_bwd_lookup_grad(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
-                             int64_t dy_stride_t, int64_t dy_stride_b, int ste, int64_t* rows, float* vals,
-                             void* stream) {
-    int rc = check_set(set);
-    if (rc) return rc;
-    if ((rc = check_batch(batch, "dqrm_emb_bwd_lookup_grad"))) return rc;
-    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_lookup_grad"))) return rc;
-    if (!rows || !vals || (((uintptr_t)vals) & 15))
-        return set_error(DQRM_E_INVALID, "%s: rows / 16-B aligned vals required", "dqrm_emb_bwd_lookup_grad");
-    if (batch->num_bags <= 0) return DQRM_OK;
-    LgArgs a;
-    a.meta = set->meta; a.scale = set->scale; a.err = (uint32_t*)set->err; a.idx = batch->idx; a.off = batch->off;
-    a.idx_base = batch->idx_base; a.dy = dy; a.dst_t = dy_stride_t; a.dst_b = dy_stride_b; a.B = batch->num_bags;
-    a.rows = rows; a.vals = vals; a.T = set->num_tables; a.ste = ste;
-    a.pool1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_LPR(set->dim, {
-        constexpr int G = 256 / LPR;
-        int64_t gx = (a.B + G - 1) / G;
-        if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(k_lookup_grad<LPR>, dim3((unsigned)gx, (unsigned)a.T), dim3(256), 0, st, a);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
 
 int64_t dqrm_coalesce_slot_caps(const int64_t* num_rows_host, int num_tables, int64_t max_lookups,
                                 int64_t* ws_cap_base_host) {
@@ -5202,68 +4474,6 @@ size_t dqrm_payload_bytes(int num_tables, int64_t cap_total, int dim, int grad_b
     return (size_t)payload_layout(num_tables, cap_total, dim, grad_bits).bytes;
 }
 
-int dqrm_grad_quant_pack_strided(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
-                                 const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
-                                 const float* absmax_all, int64_t absmax_pitch, int num_ranks, int grad_bits,
-                                 const int64_t* cap_base, int64_t cap_total, float* s_avg, void* payload,
-                                 void* stream) {
-    if (num_tables <= 0 || num_tables > MAX_TABLES || num_ranks <= 0 || num_ranks > 64)
-        return set_error(DQRM_E_INVALID, "%s: bad num_tables/num_ranks", "dqrm_grad_quant_pack");
-    if (!(grad_bits == 32 || (grad_bits >= 2 && grad_bits <= 16)))
-        return set_error(DQRM_E_INVALID, "%s: grad bits %d unsupported", "dqrm_grad_quant_pack", grad_bits);
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !cap_base || !payload ||
-        (grad_bits != 32 && (!absmax_all || !s_avg)))
-        return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_grad_quant_pack");
-    if (num_ranks > 1 && absmax_pitch < (int64_t)num_tables * SPLIT)
-        return set_error(DQRM_E_INVALID, "%s: absmax pitch %lld < %d", "dqrm_grad_quant_pack",
-                         (long long)absmax_pitch, num_tables * SPLIT);
-    if (((uintptr_t)payload) & 15)
-        return set_error(DQRM_E_INVALID, "%s: payload must be 16-B aligned", "dqrm_grad_quant_pack");
-    hipStream_t st = (hipStream_t)stream;
-    if (!dqrm_internal::env_qpack_legacy()) {  // (legacy: the one-workgroup-per-slot kernel, A/B)
-        dqrm_internal::QuantPackArgs q{num_tables, dim, ws_cap_base, ws_rows, ws_vals, ws_ucount, absmax_all,
-                                       absmax_pitch, num_ranks, grad_bits, cap_base, cap_total, s_avg,
-                                       (unsigned char*)payload};
-        DQRM_HIP_TRY(dqrm_internal::launch_quant_pack(q, st));
-        return DQRM_OK;
-    }
-    DISPATCH_LPR(dim, {
-        hipLaunchKernelGGL(k_quant_pack<LPR>, dim3(num_tables * SPLIT), dim3(512), 0, st,
-                           num_tables, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount, absmax_all,
-                           absmax_pitch, num_ranks, grad_bits, cap_base, cap_total, s_avg, (unsigned char*)payload,
-                           (const int32_t*)nullptr, (const float*)nullptr);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-int dqrm_grad_quant_pack(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
-                         const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
-                         const float* absmax_all, int num_ranks, int grad_bits, const int64_t* cap_base,
-                         int64_t cap_total, float* s_avg, void* payload, void* stream) {
-    return dqrm_grad_quant_pack_strided(num_tables, dim, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount,
-                                        absmax_all, (int64_t)num_tables * SPLIT, num_ranks, grad_bits, cap_base,
-                                        cap_total, s_avg, payload, stream);
-}
-
-int dqrm_grad_quant_pack_ranked(int num_tables, int dim, const int64_t* ws_cap_base, int64_t ws_cap_total,
-                                const int32_t* ws_rows, const float* ws_vals, const int32_t* ws_ucount,
-                                const int32_t* table_bits, const float* table_scale, const int64_t* cap_base,
-                                int64_t cap_total, void* payload, void* stream) {
-    if (num_tables <= 0 || num_tables > MAX_TABLES)
-        return set_error(DQRM_E_INVALID, "%s: bad num_tables", "dqrm_grad_quant_pack_ranked");
-    if (!ws_cap_base || !ws_rows || !ws_vals || !ws_ucount || !table_bits || !table_scale || !cap_base || !payload)
-        return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_grad_quant_pack_ranked");
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_LPR(dim, {
-        hipLaunchKernelGGL(k_quant_pack<LPR>, dim3(num_tables * SPLIT), dim3(512), 0, st,
-                           num_tables, ws_cap_base, ws_cap_total, ws_rows, ws_vals, ws_ucount,
-                           (const float*)nullptr, (int64_t)0, 1, 8, cap_base, cap_total, (float*)nullptr,
-                           (unsigned char*)payload, table_bits, table_scale);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
 
 int dqrm_emb_local_update(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
                           int64_t dy_stride_t, int64_t dy_stride_b, int ste, float lr, const int32_t* table_mask,
@@ -5428,75 +4638,5 @@ int dqrm_bwd_sgd_fwd_is_one_launch(const dqrm_table_set* set, const dqrm_batch* 
     return sgd_plan(set, batch, next, fwd_flags).fwd_inside ? 1 : 0;
 }
 
-int dqrm_read_errors(const dqrm_table_set* set, uint32_t* flags, int clear, void* stream) {
-    if (!set || !set->err || !flags) return set_error(DQRM_E_INVALID, "%s: null pointer", "dqrm_read_errors");
-    hipStream_t st = (hipStream_t)stream;
-    DQRM_HIP_TRY(hipMemcpyAsync(flags, set->err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DQRM_HIP_TRY(hipStreamSynchronize(st));
-    if (clear) DQRM_HIP_TRY(hipMemsetAsync(set->err, 0, sizeof(uint32_t), st));
-    return DQRM_OK;
-}
-
-
-// ---------------------------------------------------------------------------------
-// Row-wise PTQ formats
-// ---------------------------------------------------------------------------------
-#define DISPATCH_G(D, ...)                                                               \
-    switch ((D) % 8 ? 0 : (D) / 8) {                                                     \
-        case 1: { constexpr int G = 1; __VA_ARGS__; } break;                             \
-        case 2: { constexpr int G = 2; __VA_ARGS__; } break;                             \
-        case 4: { constexpr int G = 4; __VA_ARGS__; } break;                             \
-        case 8: { constexpr int G = 8; __VA_ARGS__; } break;                             \
-        case 16: { constexpr int G = 16; __VA_ARGS__; } break;                           \
-        case 32: { constexpr int G = 32; __VA_ARGS__; } break;                           \
-        default: return set_error(DQRM_E_INVALID, "dqrm rowwise: dim %d unsupported", (int)(D)); \
-    }
-
-size_t dqrm_rowwise_row_bytes(int bits, int dim) {
-    if ((bits != 4 && bits != 8) || dim < 8 || (dim & 7)) return 0;
-    return (size_t)rowwise_row_bytes(bits, dim);
-}
-
-int dqrm_rowwise_prepack(int bits, const float* W, int64_t num_rows, int dim, uint8_t* packed, void* stream) {
-    if (bits != 4 && bits != 8) return set_error(DQRM_E_INVALID, "dqrm_rowwise_prepack: bits must be 4 or 8");
-    if (!W || !packed || num_rows < 0) return set_error(DQRM_E_INVALID, "dqrm_rowwise_prepack: bad arguments");
-    if (((uintptr_t)W) & 15) return set_error(DQRM_E_INVALID, "dqrm_rowwise_prepack: W must be 16-byte aligned");
-    if (num_rows == 0) return DQRM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_G(dim, {
-        const int rows_per_wg = 256 / G;
-        const int grid = grid_for(num_rows, rows_per_wg, 65536);
-        if (bits == 4)
-            hipLaunchKernelGGL((k_rowwise_prepack<4, G>), dim3(grid), dim3(256), 0, st, W, num_rows, packed);
-        else
-            hipLaunchKernelGGL((k_rowwise_prepack<8, G>), dim3(grid), dim3(256), 0, st, W, num_rows, packed);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
-
-int dqrm_rowwise_bag(int bits, const uint8_t* packed, int64_t num_rows, int dim, const int64_t* idx,
-                     int64_t num_lookups, const int64_t* off, int64_t num_bags, int include_last_offset,
-                     const float* per_sample_weights, float* out, uint32_t* err, void* stream) {
-    if (bits != 4 && bits != 8) return set_error(DQRM_E_INVALID, "dqrm_rowwise_bag: bits must be 4 or 8");
-    if (!packed || !off || !out || !err || (num_lookups > 0 && !idx) || num_rows < 0 || num_lookups < 0)
-        return set_error(DQRM_E_INVALID, "dqrm_rowwise_bag: bad arguments");
-    if (((uintptr_t)packed) & 3 || ((uintptr_t)out) & 15)
-        return set_error(DQRM_E_INVALID, "dqrm_rowwise_bag: packed must be 4-B and out 16-B aligned");
-    if (num_bags <= 0) return DQRM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DISPATCH_G(dim, {
-        const int bags_per_wg = 256 / G;
-        const int grid = grid_for(num_bags, bags_per_wg, 65536);
-        if (bits == 4)
-            hipLaunchKernelGGL((k_rowwise_bag<4, G>), dim3(grid), dim3(256), 0, st, packed, num_rows, idx,
-                               num_lookups, off, num_bags, per_sample_weights, include_last_offset, out, err);
-        else
-            hipLaunchKernelGGL((k_rowwise_bag<8, G>), dim3(grid), dim3(256), 0, st, packed, num_rows, idx,
-                               num_lookups, off, num_bags, per_sample_weights, include_last_offset, out, err);
-    });
-    LAUNCH_CHECK();
-    return DQRM_OK;
-}
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 // identity, in any order), so W is bit-identical run to run and the COO still sums to the
 // same per-row gradient.
 //
-// One 1024-thread workgroup per table (<= kPresumMaxL lookups; larger tables keep the plain
+// One 1024-thread workgroup per table (<= PS_MAXL lookups; larger tables keep the plain
 // per-lookup gradient): rows into an LDS hash (linear probing, arrival rank per lookup), the
 // rows' lookup lists laid out by a block scan of their counts, each list put in lookup order
 // by counting, then one lane group (LPR lanes x float4) per lookup writes its entry -- a
@@ -24,10 +24,38 @@
 #include "dqrm_device.h"
 #include "dqrm_internal.h"
 
+namespace dqrm_internal {
+
+// k_lookup_grad_presum's arguments (dqrm_emb_bwd_lookup_grad_presum's, validated)
+struct PresumArgs {
+    const int64_t* meta;
+    const float* scale;
+    uint32_t* err;
+    const int64_t* idx;
+    const int64_t* off;
+    const int64_t* idx_base;
+    const float* dy;
+    int64_t dst_t, dst_b;
+    int64_t B;
+    int64_t* rows;
+    float* vals;
+    int T;
+    int D;
+    int ste;
+    int pool1;
+};
+
+}  // namespace dqrm_internal
+
 namespace {
 
+using dqrm_internal::check_batch;
+using dqrm_internal::check_dy;
+using dqrm_internal::check_set;
+using dqrm_internal::set_error;
+
 constexpr int PS_TPB = 1024;
-constexpr int PS_MAXL = dqrm_internal::kPresumMaxL;
+constexpr int PS_MAXL = DQRM_PRESUM_MAX_LOOKUPS;
 constexpr int PS_HLOG = 12;                  // 4096 hash slots: load <= 1/2
 constexpr int PS_HSIZE = 1 << PS_HLOG;
 constexpr int PS_PER = PS_MAXL / PS_TPB;     // lookups per thread
@@ -197,35 +225,117 @@ __global__ void __launch_bounds__(PS_TPB) k_lookup_grad_presum(dqrm_internal::Pr
     }
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------
+// Per-lookup (uncoalesced) sparse gradient, the form nn.EmbeddingBag(sparse=True) hands to
+// autograd (embedding_bag_backward's sparse branch: indices = the input indices, values =
+// the bag's gradient row once per lookup, in lookup order): lookup j of table t gets
+// rows[j] = row_base[t] + idx[j] and vals[j] = (dy[t, bag(j)] * s_t) / s_t (STE,
+// quant_utils.py:349-363). One lane group per bag, its dy row loaded once and stored for
+// each of its lookups (coalesced float4 stores), grid (bag chunks, tables).
+// ------------------------------------------------------------------------------------
+struct LgArgs {
+    const int64_t* meta;
+    const float* scale;
+    uint32_t* err;
+    const int64_t* idx;
+    const int64_t* off;
+    const int64_t* idx_base;
+    const float* dy;
+    int64_t dst_t, dst_b;
+    int64_t B;
+    int64_t* rows;
+    float* vals;
+    int T;
+    int ste;
+    int pool1;
+};
 
-namespace dqrm_internal {
-
-hipError_t launch_lookup_grad_presum(const PresumArgs& a, hipStream_t stream) {
-    switch (a.D) {
-#define PS_CASE(Dd)                                                                                        \
-    case Dd: hipLaunchKernelGGL(k_lookup_grad_presum<Dd / 4>, dim3(a.T), dim3(PS_TPB), 0, stream, a); break;
-        PS_CASE(4) PS_CASE(8) PS_CASE(16) PS_CASE(32) PS_CASE(64) PS_CASE(128) PS_CASE(256)
-#undef PS_CASE
-        default: return hipErrorInvalidValue;
+template <int LPR>
+__global__ void __launch_bounds__(256) k_lookup_grad(LgArgs a) {
+    const int t = blockIdx.y;
+    constexpr int G = 256 / LPR;
+    const int lane = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    const int D = LPR * 4;
+    const float s = a.scale[t];
+    const int64_t rowbase = a.meta[t], nrows = a.meta[a.T + t];
+    // Criteo form: table t's lookups are idx[t*B, (t+1)*B) -- no idx_base round trip in front of the index loads
+    const int64_t ibase = a.pool1 ? (int64_t)t * a.B : a.idx_base[t];
+    const int64_t L = a.pool1 ? a.B : a.idx_base[t + 1] - ibase;
+    const int64_t B = a.B;
+    const int64_t* __restrict__ off = a.off + (int64_t)t * B;
+    const bool p1 = a.pool1 && L == B;
+    for (int64_t b = (int64_t)blockIdx.x * G + grp; b < B; b += (int64_t)gridDim.x * G) {
+        int64_t s0 = p1 ? b : off[b];
+        int64_t s1 = p1 ? b + 1 : ((b + 1 < B) ? off[b + 1] : L);
+        if (s0 < 0 || s1 > L || s1 < s0 || (b == 0 && s0 != 0)) {  // nn.EmbeddingBag needs off[0] == 0
+            if (lane == 0) flag_error(a.err, DQRM_ERRF_OFFSET);
+            s0 = s0 < 0 ? 0 : (s0 > L ? L : s0);
+            s1 = s1 < s0 ? s0 : (s1 > L ? L : s1);
+            if (b == 0)  // lookups before the first bag: zero rows on the table's row 0, never garbage
+                for (int64_t j = 0; j < s0; ++j) {
+                    if (lane == 0) a.rows[ibase + j] = rowbase;
+                    reinterpret_cast<float4*>(a.vals + (ibase + j) * D)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+        }
+        if (s1 == s0) continue;
+        float4 g = reinterpret_cast<const float4*>(a.dy + (int64_t)t * a.dst_t + b * a.dst_b)[lane];
+        if (a.ste) { g.x = (g.x * s) / s; g.y = (g.y * s) / s; g.z = (g.z * s) / s; g.w = (g.w * s) / s; }
+        for (int64_t j = s0; j < s1; ++j) {
+            int64_t r = a.idx[ibase + j];
+            float4 v = g;
+            if (r < 0 || r >= nrows) {  // flagged; the entry becomes a zero row on the table's row 0
+                if (lane == 0) flag_error(a.err, DQRM_ERRF_INDEX);
+                r = 0;
+                v = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            if (lane == 0) a.rows[ibase + j] = rowbase + r;
+            reinterpret_cast<float4*>(a.vals + (ibase + j) * D)[lane] = v;
+        }
     }
-    return hipGetLastError();
 }
 
-}  // namespace dqrm_internal
+}  // namespace
 
-extern "C" int dqrm_emb_bwd_lookup_grad_presum(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
-                                               int64_t dy_stride_t, int64_t dy_stride_b, int ste, int64_t* rows,
-                                               float* vals, void* stream) {
+extern "C" {
+
+int dqrm_emb_bwd_lookup_grad(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
+                             int64_t dy_stride_t, int64_t dy_stride_b, int ste, int64_t* rows, float* vals,
+                             void* stream) {
+    int rc = check_set(set);
+    if (rc) return rc;
+    if ((rc = check_batch(batch, "dqrm_emb_bwd_lookup_grad"))) return rc;
+    if ((rc = check_dy(dy, dy_stride_t, dy_stride_b, "dqrm_emb_bwd_lookup_grad"))) return rc;
+    if (!rows || !vals || (((uintptr_t)vals) & 15))
+        return set_error(DQRM_E_INVALID, "%s: rows / 16-B aligned vals required", "dqrm_emb_bwd_lookup_grad");
+    if (batch->num_bags <= 0) return DQRM_OK;
+    LgArgs a;
+    a.meta = set->meta; a.scale = set->scale; a.err = (uint32_t*)set->err; a.idx = batch->idx; a.off = batch->off;
+    a.idx_base = batch->idx_base; a.dy = dy; a.dst_t = dy_stride_t; a.dst_b = dy_stride_b; a.B = batch->num_bags;
+    a.rows = rows; a.vals = vals; a.T = set->num_tables; a.ste = ste;
+    a.pool1 = (batch->flags & DQRM_BATCH_POOLING_ONE) != 0;
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_LPR(set->dim, {
+        constexpr int G = 256 / LPR;
+        int64_t gx = (a.B + G - 1) / G;
+        if (gx > 4096) gx = 4096;
+        hipLaunchKernelGGL(k_lookup_grad<LPR>, dim3((unsigned)gx, (unsigned)a.T), dim3(256), 0, st, a);
+    });
+    LAUNCH_CHECK();
+    return DQRM_OK;
+}
+
+int dqrm_emb_bwd_lookup_grad_presum(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy,
+                                    int64_t dy_stride_t, int64_t dy_stride_b, int ste, int64_t* rows, float* vals,
+                                    void* stream) {
+    // (its own texts where the shared validators' differ: check_set's and check_batch's do)
     const char* who = "dqrm_emb_bwd_lookup_grad_presum";
-    auto err = [&](int code, const char* what) { return dqrm_internal::set_error(code, "%s: %s", who, what); };
+    auto err = [&](int code, const char* what) { return set_error(code, "%s: %s", who, what); };
     if (!set || !batch || !set->meta || !set->scale || !set->err || set->num_tables <= 0)
         return err(DQRM_E_INVALID, "null table set / batch");
     const int D = set->dim;
     if (D < 4 || D > 256 || (D & 3) || ((D / 4) & (D / 4 - 1))) return err(DQRM_E_INVALID, "dim must be 4*2^k <= 256");
     if (!batch->idx || !batch->off || !batch->idx_base) return err(DQRM_E_INVALID, "null batch pointer");
-    if (!dy || (((uintptr_t)dy) & 15) || (dy_stride_t & 3) || (dy_stride_b & 3))
-        return err(DQRM_E_INVALID, "dy must be 16-B aligned with strides % 4 == 0");
+    if (int rc = check_dy(dy, dy_stride_t, dy_stride_b, who)) return rc;
     if (!rows || !vals || (((uintptr_t)vals) & 15)) return err(DQRM_E_INVALID, "rows / 16-B aligned vals required");
     if (batch->max_lookups > DQRM_PRESUM_MAX_LOOKUPS)
         return err(DQRM_E_CAPACITY, "a table has more than DQRM_PRESUM_MAX_LOOKUPS lookups (max_lookups)");
@@ -233,7 +343,12 @@ extern "C" int dqrm_emb_bwd_lookup_grad_presum(const dqrm_table_set* set, const 
     dqrm_internal::PresumArgs a{set->meta, set->scale, set->err, batch->idx, batch->off, batch->idx_base, dy,
                                 dy_stride_t, dy_stride_b, batch->num_bags, rows, vals, set->num_tables, D, ste,
                                 (batch->flags & DQRM_BATCH_POOLING_ONE) != 0};
-    const hipError_t e = dqrm_internal::launch_lookup_grad_presum(a, (hipStream_t)stream);
+    DISPATCH_LPR(D, {  // (D passed the check above: the default is not reached)
+        hipLaunchKernelGGL(k_lookup_grad_presum<LPR>, dim3(a.T), dim3(PS_TPB), 0, (hipStream_t)stream, a);
+    });
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return err(DQRM_E_HIP, hipGetErrorString(e));
     return DQRM_OK;
 }
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """The environment switches of libdqrm: what the sources read is what INTEGRATION.md documents,
-and every switch is read in one place (the switch block of csrc/dqrm_kernels.hip)."""
+and every switch is read in one place (the switch block of csrc/dqrm_host.hip)."""
 import glob
 import os
 import re
@@ -39,4 +39,4 @@ def test_each_switch_is_read_in_one_place():
     where = {}
     for fname, name in calls:
         where.setdefault(name, []).append(fname)
-    assert {n: w for n, w in where.items() if w != ["dqrm_kernels.hip"]} == {}
+    assert {n: w for n, w in where.items() if w != ["dqrm_host.hip"]} == {}

@@ -2,14 +2,18 @@
 """Digest of the device code of csrc translation units, to show that a host-only change left
 the kernels byte for byte as they were.
 
-    tools/device_code_digest.py [--tree DIR] [--define NAME ...] [--out FILE.json] [unit.hip ...]
+    tools/device_code_digest.py [--tree DIR] [--define NAME ...] [--out FILE.json]
+                                [--union FILE.txt] [unit.hip ...]
 
-Each unit (default: dqrm_kernels.hip and dqrm_coalesce.hip of DIR, default this checkout) is
+Each unit (default: every unit of _build.py's SOURCES in DIR, default this checkout) is
 compiled with _build.py's flags into a temporary directory; the object's .hip_fatbin section is
 dumped (llvm-objcopy) and hashed, the gfx950 code object is unbundled from it
 (clang-offload-bundler), and every function symbol and every kernel descriptor (<kernel>.kd) of
 that ELF is listed with its size and the sha256 of its bytes. The tool only hashes: it reads no
-instruction. Compare two trees with --out and `diff`, or read the section hashes.
+instruction. Compare two trees with --out and `diff`, or read the section hashes. Two trees
+whose unit lists differ (code moved between units) compare with --union: one sorted line
+"name kind size sha256" per symbol over all units, without the unit, and a summary line that
+counts the names found in more than one unit.
 
 Two things make digests of two checkouts comparable. The compile adds -cuid=<unit name>: hipcc
 otherwise derives the unit's id, a symbol name in the code object, from the source's path, so
@@ -19,6 +23,8 @@ code: templates are emitted in the order the host code first uses them, so movin
 moves kernels. The section hash then differs while every symbol's does not.
 """
 import argparse
+import collections
+from concurrent.futures import ThreadPoolExecutor
 import hashlib
 import json
 import os
@@ -42,7 +48,7 @@ def build_flags(tree):
     sys.path.insert(0, tree)
     from deep_quantized_recommendation_model_dqrm_amd import _build
 
-    return _build.hipcc(), list(_build.HIPCC_FLAGS)
+    return _build.hipcc(), list(_build.HIPCC_FLAGS), list(_build.SOURCES)
 
 
 def elf_symbols(blob):
@@ -73,12 +79,16 @@ def elf_symbols(blob):
 
 
 def digest_unit(src, tree, defines, tmp):
-    hipcc, flags = build_flags(tree)
+    hipcc, flags, _ = build_flags(tree)
     base = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0])
     obj, fat, co = base + ".o", base + ".hip_fatbin", base + ".gfx950.co"
     cmd = [hipcc, *flags, "-cuid=" + os.path.basename(base), *["-D" + d for d in defines], "-I", os.path.join(tree, "include"), "-c", src, "-o", obj]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    subprocess.run([llvm_tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
+    has_device = subprocess.run([llvm_tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj],
+                                stderr=subprocess.DEVNULL).returncode == 0
+    if not has_device:  # a unit without device code has no such section
+        return {"unit": os.path.basename(src), "defines": defines, "section_bytes": 0, "section_sha256": None,
+                "kernels": 0, "symbols": []}
     subprocess.run([llvm_tool("clang-offload-bundler"), "--unbundle", "--type=o", "--targets=" + TARGET,
                     "--input=" + fat, "--output=" + co], check=True)
     with open(fat, "rb") as f:
@@ -96,18 +106,28 @@ def main():
     ap.add_argument("--tree", default=os.path.dirname(HERE), help="checkout to digest (default: this one)")
     ap.add_argument("--define", action="append", default=[], help="extra -D (e.g. DQRM_DIAG_CLOCK)")
     ap.add_argument("--out", help="write the full digest (every symbol) as JSON")
+    ap.add_argument("--union", help="write one 'name kind size sha256' line per symbol over all units")
     ap.add_argument("units", nargs="*")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
-    csrc = os.path.join(tree, "deep_quantized_recommendation_model_dqrm_amd", "csrc")
-    units = [os.path.abspath(u) for u in a.units] or [os.path.join(csrc, n) for n in ("dqrm_kernels.hip",
-                                                                                     "dqrm_coalesce.hip")]
-    with tempfile.TemporaryDirectory() as tmp:
-        res = [digest_unit(u, tree, a.define, tmp) for u in units]
+    units = [os.path.abspath(u) for u in a.units] or build_flags(tree)[2]
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
+        res = list(pool.map(lambda u: digest_unit(u, tree, a.define, tmp), units))
     for r in res:
         allsyms = hashlib.sha256(json.dumps(r["symbols"], sort_keys=True).encode()).hexdigest()
         print(f"{r['unit']}: .hip_fatbin {r['section_bytes']} bytes sha256 {r['section_sha256']}; "
               f"{r['kernels']} kernels, {len(r['symbols'])} symbols, digest of all (name, size, sha256) {allsyms}")
+    union = sorted((s["name"], s["kind"], s["size"], s["sha256"]) for r in res for s in r["symbols"])
+    seen = collections.Counter(u[0] for u in union)
+    dup = sorted(n for n, c in seen.items() if c > 1)
+    usum = hashlib.sha256(json.dumps(union).encode()).hexdigest()
+    print(f"union of {len(res)} units: {sum(r['kernels'] for r in res)} kernels, {len(union)} symbols, "
+          f"{len(dup)} names in more than one unit, digest of all (name, kind, size, sha256) {usum}")
+    for n in dup:
+        print(f"  in more than one unit: {n}")
+    if a.union:
+        with open(a.union, "w") as f:
+            f.writelines(f"{n} {k} {z} {h}\n" for n, k, z, h in union)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)

@@ -1,12 +1,14 @@
-"""Print VGPRs / SGPRs / scratch / LDS per kernel of libdqrm (hipcc -Rpass-analysis)."""
+"""Print VGPRs / SGPRs / scratch / LDS per kernel of libdqrm (hipcc -Rpass-analysis), every unit
+of csrc/."""
+import glob
 import re
 import subprocess
 import sys
 
 ROOT = __file__.rsplit("/tools/", 1)[0]
-src = f"{ROOT}/deep_quantized_recommendation_model_dqrm_amd/csrc/dqrm_kernels.hip"
+srcs = sorted(glob.glob(f"{ROOT}/deep_quantized_recommendation_model_dqrm_amd/csrc/*.hip"))
 cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-       f"-I{ROOT}/include", "-Rpass-analysis=kernel-resource-usage", src, "-o", "/tmp/_ru.so"] + sys.argv[1:]
+       f"-I{ROOT}/include", "-Rpass-analysis=kernel-resource-usage", *srcs, "-o", "/tmp/_ru.so"] + sys.argv[1:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
