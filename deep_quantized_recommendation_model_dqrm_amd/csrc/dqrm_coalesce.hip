@@ -35,12 +35,15 @@
 //
 // The same kernel, k_coalesce_p1, is also the one-launch training step (APPLY, world size 1)
 // and that step with the next batch's forward behind it (FWD). Its stages, in the order they
-// run. Slot geometry, lookups and compaction, order, land + ordered sums and the update are still
-// sections of the kernel's body under a banner of the same name (as functions they moved the
-// kernels' descriptors or the inlining of radix_sort: DESIGN section 8 lists the forms tried);
-// the others are functions defined below the kernel, in this order (prefetch_w,
-// slot_max_and_granule, rendezvous, rereduce_owned_blocks, arrive_and_finalize, next_forward),
-// each with a comment saying what it reads, what it leaves and which LDS is dead after it:
+// run. Slot geometry, lookups and compaction, order and land + ordered sums are still sections of
+// the kernel's body under a banner of the same name. The sorts' inlining is explicit (radix_sort
+// inlined everywhere, msd_sort called), so a stage function no longer flips it, and the update
+// went out on that; the order and the land phase were tried as functions again and still moved
+// the descriptors of the four APPLY = false kernels, and msd_sort itself when it is called from
+// inside a stage function (DESIGN section 8 lists the forms and what each moved). The others are
+// functions defined below the kernel, in this order (prefetch_w, slot_max_and_granule, rendezvous,
+// update, rereduce_owned_blocks, arrive_and_finalize, next_forward), each with a comment saying
+// what it reads, what it leaves and which LDS is dead after it:
 //   slot geometry            block map, table / slot / sub-slot, rows or dimensions owned
 //   lookups and compaction   1-2 above
 //   order                    3 above; APPLY adds the distinct-rows fast path (no sort)
@@ -232,7 +235,10 @@ __device__ __forceinline__ void block_excl_scan2(int v1, int v2, int* s_w, int* 
 // most DBMAX bits (a dimension-split table's rows: one pass). Wave w owns keys
 // [w*64*kpl, (w+1)*64*kpl), 64 at a time; same-digit lanes from bit-slice ballots;
 // [digit][wave] counters, one workgroup scan per pass.
-__device__ void radix_sort(uint64_t* keys, uint64_t* tmp, int* hist, int* s_w, int n, int nbits) {
+// Inlined into every caller by attribute: at 2.8 KB it sits at the inliner's threshold, and left
+// to the inliner, extracting a stage of the kernel switched some instantiations between calling
+// and inlining it.
+__device__ __forceinline__ void radix_sort(uint64_t* keys, uint64_t* tmp, int* hist, int* s_w, int n, int nbits) {
     const int tid = threadIdx.x, lane = tid % WAVE, w = tid / WAVE;
     const int kpl = (n + TPB - 1) / TPB;
     const int i0 = w * WAVE * kpl + lane;
@@ -310,8 +316,9 @@ __device__ void radix_sort(uint64_t* keys, uint64_t* tmp, int* hist, int* s_w, i
 // into 256 buckets (rank inside a bucket from an LDS atomic: any order), then every key's
 // place inside its bucket = the number of smaller keys there (the keys are unique, so this
 // is THE sorted order; a bucket is read by its own keys only, all reads independent). A
-// bucket above FIX_MAX keys (hot rows) -> radix_sort.
-__device__ void msd_sort(uint64_t* keys, uint64_t* tmp, int* hist, int* s_w, int n, int nbits) {
+// bucket above FIX_MAX keys (hot rows) -> radix_sort. A called function in every kernel, as the
+// inliner had it (cold: only slots spanning more than CSPAN rows reach it).
+__device__ __noinline__ void msd_sort(uint64_t* keys, uint64_t* tmp, int* hist, int* s_w, int n, int nbits) {
     const int tid = threadIdx.x;
     const int sh = nbits - 8;
     int* cnt = hist;          // [256]
@@ -634,6 +641,23 @@ __device__ __forceinline__ void slot_entries(bool dsplit, int U, const int64_t* 
     const int cap = (int)(s_cb[sl + 1] - s_cb[sl]);
     nu = nu < cap ? nu : cap;
 }
+// This workgroup's entries in its slot's workspace region start here: sub-slot 0 (or a whole slot)
+// from the region's start, sub-slot 1 packed at its end. (LDS reads, not a live register.)
+__device__ __forceinline__ int64_t entry_base(const Slot& g, int U, const int64_t* s_cb) {
+    return g.j ? s_cb[g.s + 1] - U : s_cb[g.s];
+}
+// The coalesced values a row-split slot kept in the LDS stage (lds_vals) instead of the
+// workspace: entry u's float4 sub, at stage entry vb0 + u in the stage's layout.
+struct StagedVals {
+    const float* stage;
+    int SW, SP, vb0;
+    bool rmaj;
+    __device__ __forceinline__ float4 get(int u, int sub) const {
+        if (rmaj) return *reinterpret_cast<const float4*>(stage + (vb0 + u) * SW + sub * 4);
+        const float* c = stage + sub * 4 * SP + vb0 + u;
+        return make_float4(c[0], c[SP], c[2 * SP], c[3 * SP]);
+    }
+};
 
 template <bool APPLY>
 __device__ __forceinline__ void prefetch_w(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
@@ -646,6 +670,11 @@ template <bool APPLY>
 __device__ __forceinline__ void rendezvous(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
                                            const Slot& g, const Entries& en, const int64_t* s_cb, const int* s_ucnt,
                                            float& s_am, int& s_stall, int& s_upart);
+__device__ __forceinline__ bool update(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                       const Slot& g, const Entries& en, const WPrefetch& wp, bool go, const uint64_t* keys,
+                                       const uint16_t* hpos, const StagedVals& vals, bool lds_vals, float* s_newrm,
+                                       const int64_t* s_cb, const int* s_uf, const float& s_am, const float* s_sbm,
+                                       int& s_oq_n, uint32_t* s_oq_blk, float* s_oq_old, float* s_oq_sold);
 __device__ __forceinline__ void rereduce_owned_blocks(const dqrm_internal::LocalApplyArgs& la, const Slot& g, const Entries& en,
                                                       bool dirty, const uint64_t* keys, const uint16_t* hpos,
                                                       const float* s_newrm, float* s_blkrm, const int& s_oq_n,
@@ -1192,12 +1221,11 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     }
     }  // comparison sort
     CDIAG(4);
-    // ======== where the slot's entries go (declarations the next three stages share) ========
-    const int lpr_sh = __ffs(LPR) - 1;
+    // ======== where the slot's entries go (declarations the land phase and the update share) ========
     // this workgroup's entries in its slot's workspace region: sub-slot 0 (or a whole slot) from
     // its start, sub-slot 1 packed at its end (its values are scratch; its rows are written at
     // their final place, after sub-slot 0's, once the rendezvous has told it sub-slot 0's count)
-    auto ebase = [&]() -> int64_t { return j ? s_cb[s + 1] - U : s_cb[s]; };  // (LDS reads, not a live register)
+    auto ebase = [&]() -> int64_t { return entry_base(g, U, s_cb); };
     // a row-split slot whose entries fit beside the stage's multi-lookup values keeps its
     // coalesced values in the stage (entry u, dimension d at column d, index vb0 + u) instead
     // of the workspace: no HBM round trip for them (the workspace values are then not written)
@@ -1207,8 +1235,6 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     Entries en{U, 0, 0, 0, 0, 0};
     WPrefetch wp;
     prefetch_w<APPLY>(a, la, g, keys, hpos, s_cb, s_uf, s_oq_n, s_dirty, en, wp);
-    const int nu0 = en.nu0, nsbc = wp.nsbc;
-    const int64_t rb = en.rb, bb = en.bb, sbb = en.sbb, sb0 = wp.sb0;
     // ======== land + ordered sums ========
     // reads: pf (the rest of the dy straight from memory), keys, pos, hpos, mlist, sdest.
     // leaves: the coalesced rows in ws_vals / ws_rows (or the stage, lds_vals), amax per thread.
@@ -1337,151 +1363,20 @@ __global__ void __launch_bounds__(TPB) k_coalesce_p1(dqrm_internal::CoalesceArgs
     }
     CDIAG_W(6);
     // ======== the stages behind the land phase, but for the update: functions below ========
-    slot_max_and_granule<APPLY>(a, g, en, amax, nsbc, wp.sbv, s_red, s_sbm);
+    slot_max_and_granule<APPLY>(a, g, en, amax, wp.nsbc, wp.sbv, s_red, s_sbm);
     rendezvous<APPLY>(a, la, g, en, s_cb, s_ucnt, s_am, s_stall, s_upart);
     if constexpr (APPLY) {
         __syncthreads();
         CDIAG(11);
         CDIAG_W(16);  // (diagnostic build: every load of the workgroup landed, the W prefetch included)
-        // ======== update ========
-        // reads: s_am / s_stall (rendezvous), wpf / bpf / otm, s_sbm, the coalesced values (stage or
-        // workspace), keys, hpos. leaves: W / packed / rowmax of the slot's rows, growth applied,
-        // shrunk block-max holders queued (s_oq_*) or flagged (dirty), s_newrm over sdest; a stalled
-        // workgroup: its entries re-stored. dead after it: the stage's values (rereduce_owned_blocks
-        // takes the region as scratch)
-        // the update of dqrm_apply_local: s = clamp(max|g|, 1e-8) / (2^(bits-1)-1) (* 1/N,
-        // N = 1), q = clamp(round(g/s)), W += -lr * ((q * 1) * s)
-        const float sv = sym_scale(s_am, la.bits) * (float)(1.0 / 1.0);
-        const bool go = s_stall == 0;  // a stalled workgroup leaves its rows to the last arriver
-        if (go && s == 0 && j == 0 && tid == 0) la.s_avg[t] = sv;
-        const float rr = 1.0f / sv;
-        const float qlo = -(float)(1 << (la.bits - 1)), qhi = (float)((1 << (la.bits - 1)) - 1);
-        const ApplyUpdate upd{DQRM_UPD_DP, 1.0f, sv, sv, la.nlr};
-        const float r_pack = la.repack ? 1.0f / la.pscale[t] : 0.0f;
-        bool dirty = false;
-        // a workgroup that updates ONE row-range slot keeps its rows' new maxima in LDS (the
-        // stage, free by now): a shrunk block is then re-reduced from the other rows' stored
-        // maxima (untouched this launch) and these, with no wait for its own stores
-        const bool one_slot = NA == SPLIT;
+        // ======== update: update below ========
         // (LDS dead by now: the gather map sdest and the multi-lookup list mlist)
-        float* s_newrm = reinterpret_cast<float*>(sdest);  // [nu0]
+        float* s_newrm = reinterpret_cast<float*>(sdest);  // [nu0] the rows' new maxima, left by the update
         float* s_blkrm = stage;  // the re-reduction's per-wave block scratch (the update's values are dead by then)
-        // item (entry u - ua, float4 sub) of slot sl: w0 = the row's old values, oblk its
-        // block's max before this step (a stale-low superblock or table max only costs a
-        // redundant atomicMax: within the launch they only grow)
-        auto update = [&](int ua, int q, float4 w0, float oblk, float4 v) {
-            const int u = ua + (q >> lpr_sh), sub = q & (LPR - 1);
-            const int64_t x = r0 + krow(keys[hpos[u]]), grow = rb + x;
-            const float4 acc = fake_quant4_payload(v, rr, qlo, qhi);
-            float4 wn;
-            wn.x = upd(w0.x, acc.x); wn.y = upd(w0.y, acc.y); wn.z = upd(w0.z, acc.z); wn.w = upd(w0.w, acc.w);
-            reinterpret_cast<float4*>(la.W + grow * a.D)[sub] = wn;
-            if (la.repack) pack4_row(wn, la.packed + grow * (a.D / 2), sub, r_pack);
-            float old_rm = abs_max4(w0), rm = abs_max4(wn);
-            for (int o = 1; o < LPR; o <<= 1) {
-                old_rm = fmaxf(old_rm, __shfl_xor(old_rm, o, WAVE));
-                rm = fmaxf(rm, __shfl_xor(rm, o, WAVE));
-            }
-            if (sub != 0) return;
-            st_wt(la.rowmax + grow, rm);
-            if (one_slot) s_newrm[u - ua] = rm;
-            const int64_t blk = x >> 8, sb = sbb + (blk >> 8);
-            const int64_t sbl = (blk >> 8) - sb0;  // superblock index relative to the slot's first
-            const float osb = !(rm > oblk || old_rm == oblk) ? 0.0f  // the superblock's max
-                              : (sbl >= 0 && sbl < nsbc) ? s_sbm[sbl] : la.sblkmax[sb];
-            if (rm > oblk) {  // growth: order-free atomicMax on the non-negative float bits
-                atomicMax(reinterpret_cast<unsigned int*>(la.blkmax) + bb + blk, __float_as_uint(rm));
-                if (rm > osb) {
-                    atomicMax(reinterpret_cast<unsigned int*>(la.sblkmax) + sb, __float_as_uint(rm));
-                    if (rm > wp.otm) atomicMax(reinterpret_cast<unsigned int*>(la.tmax) + t, __float_as_uint(rm));
-                }
-            }
-            if (old_rm == oblk && rm < old_rm) {  // the block's max holder shrank: this slot owns the block
-                const int p = atomicAdd(&s_oq_n, 1);
-                if (p < OWN_Q) {
-                    s_oq_blk[p] = (uint32_t)blk;
-                    s_oq_old[p] = oblk;
-                    s_oq_sold[p] = osb;
-                } else {  // queue full: the finalize re-reduces it
-                    flag_set(la.bdirty, bb + blk);
-                    flag_set(la.sdirty, sb);
-                    dirty = true;
-                }
-            }
-        };
-        // the values: from the LDS stage (lds_vals), else a row split reads back its own values
-        // (plain loads after the workgroup barrier) and a dimension-split table's rows hold the
-        // slices of all its workgroups (sc1 loads)
-        auto lds_val = [&](int q) -> float4 {  // entry q >> lpr_sh, float4 q & (LPR-1)
-            if (rmaj)
-                return *reinterpret_cast<const float4*>(stage + (vb0 + (q >> lpr_sh)) * SW + (q & (LPR - 1)) * 4);
-            const float* c = stage + (q & (LPR - 1)) * 4 * SP + vb0 + (q >> lpr_sh);
-            return make_float4(c[0], c[SP], c[2 * SP], c[3 * SP]);
-        };
-        auto mem_val = [&](const float* vb, int q) -> float4 {
-            return dsplit ? ld4_sc1(vb, (uint32_t)q * 16u) : reinterpret_cast<const float4*>(vb)[q];
-        };
-        auto load_val = [&](const float* vb, int q) -> float4 { return lds_vals ? lds_val(q) : mem_val(vb, q); };
-        if (!go && !dsplit) {
-            // a row-split slot's entries [ebase, ebase + nu0) re-stored write-through (sc1: the
-            // last arriver may run on another XCD, whose L2 never saw this one's plain stores):
-            // values from the LDS stage or back from this workgroup's own workspace stores, rows
-            // from its keys (a dimension-split table's values are stored write-through already,
-            // its workgroups' hand-off; they share one XCD with their rows' writer)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            for (int q = tid; q < (nu0 << lpr_sh); q += TPB) {
-                const int u = q >> lpr_sh, sub = q & (LPR - 1);
-                const int64_t e = ebase() + u;
-                float4* dst = reinterpret_cast<float4*>(a.ws_vals + e * a.D) + sub;
-                st4_wt(dst, lds_vals ? lds_val(q) : *dst);
-                if (sub == 0)
-                    __hip_atomic_store(reinterpret_cast<uint32_t*>(a.ws_rows + e),
-                                       (uint32_t)(r0 + krow(keys[hpos[u]])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (!go && tid == 0)  // recorded before this workgroup's arrival (ordered by its vmcnt(0))
-            atomicOr(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD, 1u << (s + SPLIT * j));
-        // vmcnt counts loads and stores in issue order: a load still pending when the update's
-        // stores have been issued is waited for with vmcnt(0), i.e. after every one of them. So
-        // the prefetched W rows and block maxima (landed during the rendezvous) are waited for
-        // here, once (a real s_waitcnt vmcnt(0) the compiler's wait tracking sees; they landed
-        // during the rendezvous), and values read from memory likewise before their updates.
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt / lgkmcnt not waited
-        for (int sl = s, j0 = 0; go && sl < SPLIT; sl += NA, j0 = 1) {  // uniform
-            int ua, nu;
-            slot_entries(dsplit, U, s_cb, s_uf, sl, ua, nu);
-            const int nit = nu << lpr_sh;
-            const float* vb = a.ws_vals + (dsplit ? s_cb[sl] : ebase()) * a.D;  // the entries, D floats each
-            int q = tid;
-            if (j0 == 0) {  // the prefetched rows: value loads two at a time in flight, then the updates
-#pragma unroll
-                for (int jh = 0; jh < WPF; jh += 2) {
-                    float4 v[2];
-                    if (lds_vals) {
-#pragma unroll
-                        for (int j = jh; j < jh + 2 && j < WPF; ++j)
-                            v[j - jh] = q + TPB * j < nit ? lds_val(q + TPB * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    } else {  // landed before the updates' stores (else every later use waits for them too)
-#pragma unroll
-                        for (int j = jh; j < jh + 2 && j < WPF; ++j)
-                            v[j - jh] = q + TPB * j < nit ? mem_val(vb, q + TPB * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        __builtin_amdgcn_s_waitcnt(0x0F70);
-                    }
-#pragma unroll
-                    for (int j = jh; j < jh + 2 && j < WPF; ++j)
-                        if (q + TPB * j < nit) update(ua, q + TPB * j, wp.w[j], wp.blk[j], v[j - jh]);
-                }
-                q += TPB * WPF;
-                CDIAG(14);
-            }
-            for (; q < nit; q += TPB) {
-                const int64_t x = r0 + krow(keys[hpos[ua + (q >> lpr_sh)]]);
-                const float4 w0 = reinterpret_cast<const float4*>(la.W + (rb + x) * a.D)[q & (LPR - 1)];
-                const float ob = la.blkmax[bb + (x >> 8)];
-                update(ua, q, w0, ob, load_val(vb, q));
-            }
-        }
+        const bool go = s_stall == 0;  // a stalled workgroup leaves its rows to the last arriver
+        const StagedVals vals{stage, SW, SP, vb0, rmaj};
+        const bool dirty = update(a, la, g, en, wp, go, keys, hpos, vals, lds_vals, s_newrm, s_cb, s_uf, s_am, s_sbm,
+                                  s_oq_n, s_oq_blk, s_oq_old, s_oq_sold);
         // ======== the stages behind the update: functions below ========
         rereduce_owned_blocks(la, g, en, dirty, keys, hpos, s_newrm, s_blkrm, s_oq_n, s_oq_blk, s_oq_old, s_oq_sold,
                               s_dirty);
@@ -1669,6 +1564,152 @@ __device__ __forceinline__ void rendezvous(const dqrm_internal::CoalesceArgs& a,
         a.ws_ucount[t * SPLIT + sl] = c;
     }
     CDIAG_W(7);
+}
+
+// Stage: update (APPLY): dqrm_apply_local's arithmetic on the slot's rows.
+// Reads: s_am (rendezvous) and go (the workgroup did not stall), wp (the W prefetch, waited for
+// here), s_sbm, the coalesced values (the stage through vals when lds_vals, else the workspace),
+// keys, hpos, en, s_cb, s_uf.
+// Leaves: W / packed / rowmax of the slot's rows, growth applied, shrunk block-max holders queued
+// (s_oq_*) or flagged (returns true: some were flagged because the queue was full), the rows' new
+// maxima in s_newrm (over sdest, dead since the land phase); a stalled workgroup: its entries
+// re-stored and its stall recorded.
+// Dead after it: the stage's values (rereduce_owned_blocks takes the region as scratch).
+__device__ __forceinline__ bool update(const dqrm_internal::CoalesceArgs& a, const dqrm_internal::LocalApplyArgs& la,
+                                       const Slot& g, const Entries& en, const WPrefetch& wp, bool go, const uint64_t* keys,
+                                       const uint16_t* hpos, const StagedVals& vals, bool lds_vals, float* s_newrm,
+                                       const int64_t* s_cb, const int* s_uf, const float& s_am, const float* s_sbm,
+                                       int& s_oq_n, uint32_t* s_oq_blk, float* s_oq_old, float* s_oq_sold) {
+    const int tid = threadIdx.x, t = g.t, s = g.s, j = g.j, kd = g.kd, NA = g.NA, LPR = g.LPR, U = en.U, nu0 = en.nu0;
+    (void)kd;
+    const bool dsplit = g.dsplit;
+    const int lpr_sh = __ffs(LPR) - 1, nsbc = wp.nsbc;
+    const int64_t r0 = g.r0, rb = en.rb, bb = en.bb, sbb = en.sbb, sb0 = wp.sb0;
+    // the update of dqrm_apply_local: s = clamp(max|g|, 1e-8) / (2^(bits-1)-1) (* 1/N,
+    // N = 1), q = clamp(round(g/s)), W += -lr * ((q * 1) * s)
+    const float sv = sym_scale(s_am, la.bits) * (float)(1.0 / 1.0);
+    if (go && s == 0 && j == 0 && tid == 0) la.s_avg[t] = sv;
+    const float rr = 1.0f / sv;
+    const float qlo = -(float)(1 << (la.bits - 1)), qhi = (float)((1 << (la.bits - 1)) - 1);
+    const ApplyUpdate upd{DQRM_UPD_DP, 1.0f, sv, sv, la.nlr};
+    const float r_pack = la.repack ? 1.0f / la.pscale[t] : 0.0f;
+    bool dirty = false;
+    // a workgroup that updates ONE row-range slot keeps its rows' new maxima in LDS (the
+    // stage, free by now): a shrunk block is then re-reduced from the other rows' stored
+    // maxima (untouched this launch) and these, with no wait for its own stores
+    const bool one_slot = NA == SPLIT;
+    // item (entry u - ua, float4 sub) of slot sl: w0 = the row's old values, oblk its
+    // block's max before this step (a stale-low superblock or table max only costs a
+    // redundant atomicMax: within the launch they only grow)
+    auto update_item = [&](int ua, int q, float4 w0, float oblk, float4 v) {
+        const int u = ua + (q >> lpr_sh), sub = q & (LPR - 1);
+        const int64_t x = r0 + krow(keys[hpos[u]]), grow = rb + x;
+        const float4 acc = fake_quant4_payload(v, rr, qlo, qhi);
+        float4 wn;
+        wn.x = upd(w0.x, acc.x); wn.y = upd(w0.y, acc.y); wn.z = upd(w0.z, acc.z); wn.w = upd(w0.w, acc.w);
+        reinterpret_cast<float4*>(la.W + grow * a.D)[sub] = wn;
+        if (la.repack) pack4_row(wn, la.packed + grow * (a.D / 2), sub, r_pack);
+        float old_rm = abs_max4(w0), rm = abs_max4(wn);
+        for (int o = 1; o < LPR; o <<= 1) {
+            old_rm = fmaxf(old_rm, __shfl_xor(old_rm, o, WAVE));
+            rm = fmaxf(rm, __shfl_xor(rm, o, WAVE));
+        }
+        if (sub != 0) return;
+        st_wt(la.rowmax + grow, rm);
+        if (one_slot) s_newrm[u - ua] = rm;
+        const int64_t blk = x >> 8, sb = sbb + (blk >> 8);
+        const int64_t sbl = (blk >> 8) - sb0;  // superblock index relative to the slot's first
+        const float osb = !(rm > oblk || old_rm == oblk) ? 0.0f  // the superblock's max
+                          : (sbl >= 0 && sbl < nsbc) ? s_sbm[sbl] : la.sblkmax[sb];
+        if (rm > oblk) {  // growth: order-free atomicMax on the non-negative float bits
+            atomicMax(reinterpret_cast<unsigned int*>(la.blkmax) + bb + blk, __float_as_uint(rm));
+            if (rm > osb) {
+                atomicMax(reinterpret_cast<unsigned int*>(la.sblkmax) + sb, __float_as_uint(rm));
+                if (rm > wp.otm) atomicMax(reinterpret_cast<unsigned int*>(la.tmax) + t, __float_as_uint(rm));
+            }
+        }
+        if (old_rm == oblk && rm < old_rm) {  // the block's max holder shrank: this slot owns the block
+            const int p = atomicAdd(&s_oq_n, 1);
+            if (p < OWN_Q) {
+                s_oq_blk[p] = (uint32_t)blk;
+                s_oq_old[p] = oblk;
+                s_oq_sold[p] = osb;
+            } else {  // queue full: the finalize re-reduces it
+                flag_set(la.bdirty, bb + blk);
+                flag_set(la.sdirty, sb);
+                dirty = true;
+            }
+        }
+    };
+    // the values: from the LDS stage (lds_vals), else a row split reads back its own values
+    // (plain loads after the workgroup barrier) and a dimension-split table's rows hold the
+    // slices of all its workgroups (sc1 loads)
+    auto lds_val = [&](int q) -> float4 { return vals.get(q >> lpr_sh, q & (LPR - 1)); };
+    auto mem_val = [&](const float* vb, int q) -> float4 {
+        return dsplit ? ld4_sc1(vb, (uint32_t)q * 16u) : reinterpret_cast<const float4*>(vb)[q];
+    };
+    auto load_val = [&](const float* vb, int q) -> float4 { return lds_vals ? lds_val(q) : mem_val(vb, q); };
+    if (!go && !dsplit) {
+        // a row-split slot's entries [ebase, ebase + nu0) re-stored write-through (sc1: the
+        // last arriver may run on another XCD, whose L2 never saw this one's plain stores):
+        // values from the LDS stage or back from this workgroup's own workspace stores, rows
+        // from its keys (a dimension-split table's values are stored write-through already,
+        // its workgroups' hand-off; they share one XCD with their rows' writer)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        for (int q = tid; q < (nu0 << lpr_sh); q += TPB) {
+            const int u = q >> lpr_sh, sub = q & (LPR - 1);
+            const int64_t e = entry_base(g, U, s_cb) + u;
+            float4* dst = reinterpret_cast<float4*>(a.ws_vals + e * a.D) + sub;
+            st4_wt(dst, lds_vals ? lds_val(q) : *dst);
+            if (sub == 0)
+                __hip_atomic_store(reinterpret_cast<uint32_t*>(a.ws_rows + e),
+                                   (uint32_t)(r0 + krow(keys[hpos[u]])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (!go && tid == 0)  // recorded before this workgroup's arrival (ordered by its vmcnt(0))
+        atomicOr(la.sync + (int64_t)t * DQRM_SYNC_STRIDE + STALL_WORD, 1u << (s + SPLIT * j));
+    // vmcnt counts loads and stores in issue order: a load still pending when the update's
+    // stores have been issued is waited for with vmcnt(0), i.e. after every one of them. So
+    // the prefetched W rows and block maxima (landed during the rendezvous) are waited for
+    // here, once (a real s_waitcnt vmcnt(0) the compiler's wait tracking sees; they landed
+    // during the rendezvous), and values read from memory likewise before their updates.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt / lgkmcnt not waited
+    for (int sl = s, j0 = 0; go && sl < SPLIT; sl += NA, j0 = 1) {  // uniform
+        int ua, nu;
+        slot_entries(dsplit, U, s_cb, s_uf, sl, ua, nu);
+        const int nit = nu << lpr_sh;
+        const float* vb = a.ws_vals + (dsplit ? s_cb[sl] : entry_base(g, U, s_cb)) * a.D;  // the entries, D floats each
+        int q = tid;
+        if (j0 == 0) {  // the prefetched rows: value loads two at a time in flight, then the updates
+#pragma unroll
+            for (int jh = 0; jh < WPF; jh += 2) {
+                float4 v[2];
+                if (lds_vals) {
+#pragma unroll
+                    for (int j = jh; j < jh + 2 && j < WPF; ++j)
+                        v[j - jh] = q + TPB * j < nit ? lds_val(q + TPB * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+                } else {  // landed before the updates' stores (else every later use waits for them too)
+#pragma unroll
+                    for (int j = jh; j < jh + 2 && j < WPF; ++j)
+                        v[j - jh] = q + TPB * j < nit ? mem_val(vb, q + TPB * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    __builtin_amdgcn_s_waitcnt(0x0F70);
+                }
+#pragma unroll
+                for (int j = jh; j < jh + 2 && j < WPF; ++j)
+                    if (q + TPB * j < nit) update_item(ua, q + TPB * j, wp.w[j], wp.blk[j], v[j - jh]);
+            }
+            q += TPB * WPF;
+            CDIAG(14);
+        }
+        for (; q < nit; q += TPB) {
+            const int64_t x = r0 + krow(keys[hpos[ua + (q >> lpr_sh)]]);
+            const float4 w0 = reinterpret_cast<const float4*>(la.W + (rb + x) * a.D)[q & (LPR - 1)];
+            const float ob = la.blkmax[bb + (x >> 8)];
+            update_item(ua, q, w0, ob, load_val(vb, q));
+        }
+    }
+    return dirty;
 }
 
 // Stage: owned-block re-reduction (APPLY). Opens with the barrier behind the update.

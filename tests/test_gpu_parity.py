@@ -1077,6 +1077,29 @@ def test_sgd_small_criteo_form_matches_oracle(dq, B, D, dist):
         assert torch.equal(x, y)
 
 
+def hot_row_sort_slots(rows, P):
+    """The (table, slot, part) of a [T, B] Criteo-form batch that reach k_coalesce_p1's hot-row
+    sort (msd_sort's crowded bucket -> radix_sort): a row-split slot, whole or either half (a
+    table with sub-slots), that spans more than CSPAN = 4096 rows, with more than FIX_MAX = 64 of
+    its lookups sharing the top 8 bits of row - r0, not all on distinct rows (the one-launch step
+    does not sort distinct rows). Slot geometry as in the kernel: 256-row blocks, 8 slots."""
+    out = []
+    for t, n in enumerate(rows):
+        nblk = (n + 255) // 256
+        for s in range(8 if nblk >= 8 else 0):
+            b0, b1 = nblk * s // 8, nblk * (s + 1) // 8
+            bm = (b0 + b1) // 2
+            for part, (x0, x1) in (("whole", (b0, b1)), ("lower", (b0, bm)), ("upper", (bm, b1))):
+                r0, r1 = x0 * 256, min(x1 * 256, n)
+                if r1 - r0 <= 4096:
+                    continue
+                rel = P[t][(P[t] >= r0) & (P[t] < r1)] - r0
+                shift = int(r1 - r0 - 1).bit_length() - 8
+                if rel.size > np.unique(rel).size and np.bincount(rel >> shift).max() > 64:
+                    out.append((t, s, part))
+    return out
+
+
 @pytest.mark.parametrize("D,B,dist,layout,refresh,full", [(64, 2048, "uniform", "tbd", True, False),
                                                           (64, 2048, "zipf", "btd", True, False),
                                                           (16, 2048, "uniform", "btd", True, False),
@@ -1101,6 +1124,10 @@ def test_fused_next_forward_matches_separate_calls(dq, D, B, dist, layout, refre
     Ps[2][5, 9] = -2       # negative on a row-split table
     bs = [dq.LookupBatch.pooling_one(torch.from_numpy(P).cuda()) for P in Ps]
     assert sets[0].apply_fwd_local_is_one_launch(bs[0], bs[1])
+    if dist == "zipf":  # every step's batch sends a row-split slot through the hot-row sort (D = 64, 16: both
+        for P in Ps[:4]:  # stage layouts), whether or not the plan gives the slot's table sub-slots
+            hot = hot_row_sort_slots(rows, P)
+            assert any((t, s, "whole") in hot and part != "whole" for t, s, part in hot), hot
     kw = dict(refresh_scale=refresh, full_precision=full, layout=layout)
     ys = [ts.forward(bs[0], **kw) for ts in sets]
     assert torch.equal(ys[0], ys[1])
