@@ -21,6 +21,9 @@ Drop-in for the reference's hot path (YangZhou08/Deep_Quantized_Recommendation_M
                                                                 and the MLP's per-channel INT8 grads)
   * ``sgd_quantized_gradients`` simulated-DP buffer helpers     (embedding tables and the MLP's
                                                                 error-compensated INT8 gradients)
+  * ``quant_learned_step_size_quan.QuantEmbeddingBagLSQ`` and ``quant_pact_dorefa.QuantEmbeddingBagPACT``
+                                                               (the --quant-mode lsq | pact embedding
+                                                                baselines, fused; T-table collections)
   * ``quantized_ops.ops.quantized.embedding_bag_{4bit,byte}_*``  (row-wise PTQ inference formats)
   * ``DLRM_Net.quantize_embedding`` and the quantized ``apply_emb`` (``DQRMNet.quantize_embedding`` /
                                                                 ``RowwiseTableSet``: all tables' row-wise
@@ -42,6 +45,9 @@ from .loss import DLRMLoss, loss_fn_wrap
 from .rowwise import RowwiseTableSet
 from .model import DQRMNet
 from .metrics import DLRMMetrics
+from . import quant_learned_step_size_quan, quant_pact_dorefa
+from .quant_learned_step_size_quan import LSQEmbeddingBagCollection, LsqQuan, QuantEmbeddingBagLSQ
+from .quant_pact_dorefa import PACTEmbeddingBagCollection, QuantEmbeddingBagPACT
 from . import quantized_ops
 
 __all__ = [
@@ -76,6 +82,13 @@ __all__ = [
     "DQRMNet",
     "RowwiseTableSet",
     "DLRMMetrics",
+    "LsqQuan",
+    "QuantEmbeddingBagLSQ",
+    "LSQEmbeddingBagCollection",
+    "QuantEmbeddingBagPACT",
+    "PACTEmbeddingBagCollection",
+    "quant_learned_step_size_quan",
+    "quant_pact_dorefa",
     "quant_modules_not_quantize_grad",
     "sgd_quantized_gradients",
     "sgd_quantized_gradients_parallel_comm",

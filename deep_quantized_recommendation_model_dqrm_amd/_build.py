@@ -20,7 +20,7 @@ SOURCES = [os.path.join(CSRC_DIR, f) for f in ("dqrm_kernels.hip", "dqrm_coalesc
                                                 "dqrm_comm.hip", "dqrm_apply.hip", "dqrm_apply_merge.hip",
                                                 "dqrm_linear.hip", "dqrm_interact.hip", "dqrm_act.hip", "dqrm_loss.hip",
                                                 "dqrm_mlp.hip", "dqrm_model.hip", "dqrm_metrics.hip",
-                                                "dqrm_rowwise.hip")]
+                                                "dqrm_rowwise.hip", "dqrm_quantizers.hip")]
 DEVICE_HEADER = os.path.join(CSRC_DIR, "dqrm_device.h")
 HEADER = os.path.join(REPO_DIR, "include", "dqrm.h")
 INTERNAL_HEADER = os.path.join(CSRC_DIR, "dqrm_internal.h")

@@ -172,6 +172,13 @@ EXPORTED_SYMBOLS = (
     "dqrm_model_fwd_rowwise_workspace_bytes",
     "dqrm_model_fwd_rowwise_workspace_layout",
     "dqrm_model_fwd_rowwise_launches",
+    "dqrm_emb_fwd_lsq",
+    "dqrm_emb_fwd_lsq_launches",
+    "dqrm_emb_bwd_lsq_workspace_bytes",
+    "dqrm_emb_bwd_lsq",
+    "dqrm_emb_bwd_lsq_launches",
+    "dqrm_emb_fwd_pact",
+    "dqrm_emb_fwd_pact_launches",
     "dqrm_init_uniform",
     "dqrm_checksum64",
     "dqrm_replica_mean",
@@ -588,6 +595,15 @@ def load(path: str | None = None) -> C.CDLL:
         "dqrm_model_fwd_rowwise_workspace_bytes": (C.c_size_t, [MO, RS, C.c_int64]),
         "dqrm_model_fwd_rowwise_workspace_layout": (C.c_int, [MO, RS, C.c_int64, C.POINTER(ModelLayout)]),
         "dqrm_model_fwd_rowwise_launches": (C.c_int, [MO, RS, BA, C.c_uint32, C.c_int]),
+        "dqrm_emb_fwd_lsq": (C.c_int, [TS, BA, P, C.c_int, P, C.c_int64, C.c_int64, P, P]),
+        "dqrm_emb_fwd_lsq_launches": (C.c_int, [TS, BA]),
+        "dqrm_emb_bwd_lsq_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+        "dqrm_emb_bwd_lsq": (
+            C.c_int, [TS, BA, P, C.c_int64, C.c_int64, P, P, C.c_int, P, P, P, C.c_size_t, P]
+        ),
+        "dqrm_emb_bwd_lsq_launches": (C.c_int, [TS, BA]),
+        "dqrm_emb_fwd_pact": (C.c_int, [TS, BA, C.c_int, P, C.c_int64, C.c_int64, P]),
+        "dqrm_emb_fwd_pact_launches": (C.c_int, [TS, BA]),
         "dqrm_init_uniform": (C.c_int, [TS, C.c_uint64, P]),
         "dqrm_checksum64": (C.c_int, [P, C.c_int64, P, P]),
         "dqrm_replica_mean": (C.c_int, [P, C.c_int64, C.c_int, C.c_float, P]),

@@ -436,6 +436,77 @@ class EmbeddingTableSet:
         )
         return out
 
+    # ------------------------------------------------------------------ LSQ / PACT quantizers
+    def _out_for(self, batch: LookupBatch, out: torch.Tensor | None, layout: str) -> tuple[torch.Tensor, int, int]:
+        if batch.num_tables != self.T:
+            raise ValueError("batch has %d tables, set has %d" % (batch.num_tables, self.T))
+        B, T, D = batch.num_bags, self.T, self.D
+        if out is None:
+            out = torch.empty((T, B, D) if layout == "tbd" else (B, T, D), dtype=torch.float32, device=self.device)
+        st, sb = (B * D, D) if layout == "tbd" else (D, T * D)
+        return out, st, sb
+
+    def forward_lsq(self, batch: LookupBatch, step: torch.Tensor, bits: int = 4, out: torch.Tensor | None = None,
+                    layout: str = "tbd", keep_pooled: bool = True) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """The LSQ EmbeddingBag of every table in one launch (dqrm_emb_fwd_lsq): the bag sums
+        quantized with the learned steps `step` (f32 [T] on the device). Returns (y, pooled):
+        pooled f32 [T, B, D] holds the bag sums for backward_lsq (None with keep_pooled=False)."""
+        out, st, sb = self._out_for(batch, out, layout)
+        if step.dtype != torch.float32 or step.numel() != self.T or not step.is_contiguous() or not step.is_cuda:
+            raise ValueError("step must be a contiguous f32 [T] tensor on the device")
+        pooled = (torch.empty(self.T, batch.num_bags, self.D, dtype=torch.float32, device=self.device)
+                  if keep_pooled else None)
+        L.check(
+            self.lib.dqrm_emb_fwd_lsq(C.byref(self._c), C.byref(batch.c), _ptr(step), int(bits), _ptr(out), st, sb,
+                                      _ptr(pooled), _stream_handle()),
+            "dqrm_emb_fwd_lsq",
+        )
+        return out, pooled
+
+    def backward_lsq(self, batch: LookupBatch, dy: torch.Tensor, pooled: torch.Tensor, step: torch.Tensor,
+                     bits: int = 4, layout: str = "tbd") -> tuple[torch.Tensor, torch.Tensor]:
+        """LSQ's backward (dqrm_emb_bwd_lsq, two launches): dx f32 [T, B, D], the gradient of the
+        bag sums (the clamp's mask applied; pass it on to backward_sgd / lookup_grad with
+        ste=False), and dstep f32 [T], the steps' gradient, reduced in a fixed shape."""
+        st, sb = self._dy_strides(dy, layout, self.T, batch.num_bags, self.D)
+        dx = torch.empty(self.T, batch.num_bags, self.D, dtype=torch.float32, device=self.device)
+        # the call overwrites dstep (an empty batch launches nothing: its gradient is zero)
+        dstep = (torch.empty if batch.num_bags > 0 else torch.zeros)(self.T, dtype=torch.float32, device=self.device)
+        need = int(self.lib.dqrm_emb_bwd_lsq_workspace_bytes(self.T, batch.num_bags, self.D))
+        ws = self.__dict__.get("_lsq_ws")
+        if ws is None or ws.numel() < need:
+            ws = self._lsq_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+        L.check(
+            self.lib.dqrm_emb_bwd_lsq(C.byref(self._c), C.byref(batch.c), _ptr(dy), st, sb, _ptr(pooled), _ptr(step),
+                                      int(bits), _ptr(dx), _ptr(dstep), _ptr(ws), ws.numel(), _stream_handle()),
+            "dqrm_emb_bwd_lsq",
+        )
+        return dx, dstep
+
+    def forward_pact(self, batch: LookupBatch, bits: int = 8, out: torch.Tensor | None = None,
+                     layout: str = "tbd") -> torch.Tensor:
+        """The PACT / DoReFa EmbeddingBag of every table in one launch (dqrm_emb_fwd_pact): the
+        gathered rows mapped through tanh onto 2^bits levels, scaled by tanh of the table's
+        max |W| from the |W| hierarchy (which must be current: rows_changed / refresh_absmax
+        after W was written outside the kernels)."""
+        out, st, sb = self._out_for(batch, out, layout)
+        L.check(
+            self.lib.dqrm_emb_fwd_pact(C.byref(self._c), C.byref(batch.c), int(bits), _ptr(out), st, sb,
+                                       _stream_handle()),
+            "dqrm_emb_fwd_pact",
+        )
+        return out
+
+    def quantizer_launches(self, which: str, batch: LookupBatch) -> int:
+        """Kernels one forward_lsq / backward_lsq / forward_pact launches on `batch`
+        (which: "fwd_lsq", "bwd_lsq" or "fwd_pact"; the dqrm_emb_*_launches queries)."""
+        fn = {"fwd_lsq": self.lib.dqrm_emb_fwd_lsq_launches, "bwd_lsq": self.lib.dqrm_emb_bwd_lsq_launches,
+              "fwd_pact": self.lib.dqrm_emb_fwd_pact_launches}[which]
+        rc = fn(C.byref(self._c), C.byref(batch.c))
+        if rc < 0:
+            L.check(rc, "dqrm_emb_%s_launches" % which)
+        return rc
+
     # ------------------------------------------------------------------ backward
     def bwd_workspace(self, max_lookups: int) -> torch.Tensor:
         """Device scratch of the backward's per-table lookup sort (dqrm_bwd_workspace_bytes);

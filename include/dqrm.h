@@ -106,7 +106,12 @@ extern "C" {
                                   dqrm_mlp_fwd_qact, dqrm_mlp_bwd_qact, dqrm_model_fwd_qact,
                                   dqrm_model_step_qact, dqrm_model_qact_workspace_bytes,
                                   dqrm_model_qact_workspace_layout,
-                                  dqrm_model_qact_step_launches */
+                                  dqrm_model_qact_step_launches;
+                                  likewise within 12: the LSQ and PACT embedding quantizers
+                                  (QuantEmbeddingBagLSQ / QuantEmbeddingBagPACT): dqrm_emb_fwd_lsq,
+                                  dqrm_emb_bwd_lsq, dqrm_emb_bwd_lsq_workspace_bytes,
+                                  dqrm_emb_fwd_pact, dqrm_emb_fwd_lsq_launches,
+                                  dqrm_emb_bwd_lsq_launches, dqrm_emb_fwd_pact_launches */
 
 /* status codes */
 #define DQRM_OK            0
@@ -1339,6 +1344,59 @@ int dqrm_model_fwd_rowwise_workspace_layout(const dqrm_model* model, const dqrm_
                                             dqrm_model_layout* out);
 int dqrm_model_fwd_rowwise_launches(const dqrm_model* model, const dqrm_rowwise_set* rset, const dqrm_batch* batch,
                                     uint32_t flags, int has_labels);
+
+/* ---------------------------------------------------------------------------------
+ * The LSQ and PACT embedding quantizers, csrc/dqrm_quantizers.hip: the two baselines the
+ * reference's --quant-mode lsq|pact builds its tables from (quant_learned_step_size_quan.py:65-100
+ * with quantizer/lsq.py:18-58; quant_pact_dorefa.py:10-28, 57-112), over a dqrm_table_set and a
+ * dqrm_batch like dqrm_emb_fwd: out[t*out_stride_t + b*out_stride_b + d], either batch form
+ * (DQRM_BATCH_POOLING_ONE honoured), bag sums f32 adds in bag order from 0, an index outside
+ * [0, num_rows[t]) flags DQRM_ERRF_INDEX and contributes nothing, a bad offset pair flags
+ * DQRM_ERRF_OFFSET and is clamped. Every named step is one IEEE f32 operation (true divisions,
+ * rintf = half to even, nothing contracted). bits: 2..8. All calls validate before the first
+ * launch (DQRM_E_INVALID; a short workspace DQRM_E_WORKSPACE; a rejected call writes nothing),
+ * allocate nothing, synchronise nothing and read nothing back. num_bags == 0: nothing launched.
+ *
+ * LSQ quantizes the POOLED output with one learned step s_t per table (step[T], device):
+ *   lo = -2^(bits-1), hi = 2^(bits-1)-1, n = B*D, g = (float)(1 / sqrt((double)hi * n)) (host)
+ *   sg = s*g;  s_eff = (s - sg) + sg          (the reference's grad_scale(); not always s)
+ *   x = the bag sum;  q = x / s_eff;  r = rintf(min(max(q, lo), hi));  y = r * s_eff
+ * pooled (nullable: inference) receives x as f32 [T][B][D] for the backward. One launch.
+ *
+ * dqrm_emb_bwd_lsq, given dy (dqrm_emb_bwd_sgd's addressing) and the forward's pooled and step:
+ *   m = lo <= q <= hi (both ends inclusive);  gq = m ? dy * s_eff : 0;  dx = gq / s_eff
+ *   S1 = sum_e dy_e * r_e;  S2 = sum_e -gq_e * ((x_e / s_eff) / s_eff);  dstep[t] = (S1 + S2) * g
+ * dx f32 [T][B][D] (the per-bag row gradient, to be scattered per lookup by dqrm_emb_bwd_sgd /
+ * _lookup_grad with ste = 0) and dstep f32 [T] are overwritten. S1 and S2 are reduced in a fixed
+ * shape whose bits depend on (B, D) and the data only: elements e = b*D + d; 4096 strided chains
+ * per table (chain c takes e = c, c + 4096, ... in ascending order, acc = fmaf(a_e, b_e, acc)
+ * from 0), then a pairwise tree over the chain index (c with c^1, then pairs of pairs, ...). No
+ * float atomics, no workgroup waits on another; two launches. The workspace needs
+ * dqrm_emb_bwd_lsq_workspace_bytes(T, B, D) bytes (0 for arguments it rejects), 16-byte aligned,
+ * no initialisation.
+ *
+ * PACT / DoReFa maps every gathered weight before the bag sum, k = bits, sc = (float)(2^k - 1),
+ * mt = tanhf(tmax_t) -- the table-wide max|tanh(W)|, since tanh is odd and monotone -- so the call
+ * reads the set's tmax (which must be current, as for a refreshing dqrm_emb_fwd) and the gathered
+ * rows, never the whole table:
+ *   t = tanhf(w);  u = t / (2*mt);  a = u + 0.5;  j = rintf(sc * a);  v = 2 * (j / sc) - 1
+ * An all-zero table gives NaN (the reference's 0/0). Its backward is the identity STE: dy per
+ * lookup, dqrm_emb_bwd_sgd(..., ste = 0). One launch.
+ *
+ * The _launches queries: the kernels the call launches on these arguments (1, 2 and 1; 0 for an
+ * empty batch), <0 for a set or batch the call rejects.
+ * ------------------------------------------------------------------------------ */
+int dqrm_emb_fwd_lsq(const dqrm_table_set* set, const dqrm_batch* batch, const float* step, int bits, float* out,
+                     int64_t out_stride_t, int64_t out_stride_b, float* pooled, void* stream);
+int dqrm_emb_fwd_lsq_launches(const dqrm_table_set* set, const dqrm_batch* batch);
+size_t dqrm_emb_bwd_lsq_workspace_bytes(int num_tables, int64_t num_bags, int dim);
+int dqrm_emb_bwd_lsq(const dqrm_table_set* set, const dqrm_batch* batch, const float* dy, int64_t dy_stride_t,
+                     int64_t dy_stride_b, const float* pooled, const float* step, int bits, float* dx, float* dstep,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int dqrm_emb_bwd_lsq_launches(const dqrm_table_set* set, const dqrm_batch* batch);
+int dqrm_emb_fwd_pact(const dqrm_table_set* set, const dqrm_batch* batch, int bits, float* out, int64_t out_stride_t,
+                      int64_t out_stride_b, void* stream);
+int dqrm_emb_fwd_pact_launches(const dqrm_table_set* set, const dqrm_batch* batch);
 
 /* ---------------------------------------------------------------------------------
  * Criteo input path
