@@ -138,10 +138,24 @@ def set_default_grad_mode(mode: str) -> None:
 # bit (deterministic; ATen's GPU scatter-add orders duplicate rows by atomics), and then clears
 # .grad so the optimizer skips it. Any other optimizer, or a modified grad, gets the COO as is.
 # DQRM_SGD_HOOK=0 turns this off (the optimizer then adds the COO).
+#
+# The COO is the weight's whole gradient only if the module was called ONCE in the graph that
+# backward ran: with two calls (a shared table, two micro-batches before one backward) autograd
+# sums their COOs before it accumulates, so the second _sparse_grad of one backward voids the
+# entry (_SEVERAL, until that backward's accumulation) and the optimizer adds the sum.
+# opt.step(closure) evaluates the closure after the step pre-hooks have run, so the gradient the
+# optimizer is about to add does not exist yet when the hook looks: such a step is left to the
+# optimizer. After any optimizer step the entries of the weights it stepped are dropped (the step
+# post-hook): a COO an optimizer has added is never applied a second time by a later step.
+# opt.step(); opt.step() with no backward between: the fused step has cleared .grad, so the second
+# step finds no gradient and changes nothing (torch alone would add the kept gradient again);
+# where the optimizer added the COO itself (any fall-back above) .grad stays and torch's
+# behaviour holds.
 _SGD_HOOK = os.environ.get("DQRM_SGD_HOOK", "1") != "0"
 _SGD_OWNERS: dict = {}  # id(embedding_bag.weight) -> (weakref(weight), weakref(module)); tensors
                         # compare elementwise, so a WeakKeyDictionary cannot key them
 _SGD_HOOK_HANDLE = None
+_SEVERAL = False  # _sgd_pend while a backward runs in which the module was called more than once
 
 
 def set_fused_optimizer_step(enabled: bool) -> None:
@@ -162,6 +176,8 @@ def _sgd_step_pre_hook(opt, args, kwargs):
     weight this optimizer steps with plain SGD (see _SGD_HOOK)."""
     if not _SGD_HOOK or not _SGD_OWNERS:
         return None
+    if (args[1] if len(args) > 1 else kwargs.get("closure")) is not None:
+        return None  # the closure's backward has not run yet: what .grad holds now is not what this step adds
     for g in opt.param_groups:
         if not _plain_sgd_group(opt, g):
             continue
@@ -175,12 +191,28 @@ def _sgd_step_pre_hook(opt, args, kwargs):
     return None
 
 
+def _sgd_step_post_hook(opt, args, kwargs):
+    """torch.optim global step post-hook: whatever this optimizer stepped, its modules' entries
+    are spent (their COO was applied by the fused step, or added by the optimizer)."""
+    if not _SGD_OWNERS:
+        return
+    for g in opt.param_groups:
+        for p in g["params"]:
+            ent = _SGD_OWNERS.get(id(p))
+            if ent is None or ent[0]() is not p:
+                continue
+            m = ent[1]()
+            if m is not None and m.__dict__.get("_sgd_pend") is not None:
+                m._sgd_pend = None
+
+
 def _register_sgd_owner(module, weight: nn.Parameter) -> None:
     global _SGD_HOOK_HANDLE
     if _SGD_HOOK_HANDLE is None:
-        from torch.optim.optimizer import register_optimizer_step_pre_hook
+        from torch.optim.optimizer import register_optimizer_step_post_hook, register_optimizer_step_pre_hook
 
-        _SGD_HOOK_HANDLE = register_optimizer_step_pre_hook(_sgd_step_pre_hook)
+        _SGD_HOOK_HANDLE = (register_optimizer_step_pre_hook(_sgd_step_pre_hook),
+                            register_optimizer_step_post_hook(_sgd_step_post_hook))
     key = id(weight)
     _SGD_OWNERS[key] = (weakref.ref(weight, lambda _r, k=key: _SGD_OWNERS.pop(k, None)), weakref.ref(module))
     mref = weakref.ref(module)
@@ -190,9 +222,9 @@ def _register_sgd_owner(module, weight: nn.Parameter) -> None:
         pend = m.__dict__.get("_sgd_pend") if m is not None else None
         if pend is None:
             return
-        if pend["gid"] is None:  # the COO of the last backward, now p.grad
+        if pend is not _SEVERAL and pend["gid"] is None:  # the COO of the last backward, now p.grad
             pend["gid"], pend["gver"] = id(p.grad), p.grad._version
-        else:  # accumulated into again: the optimizer adds the sum itself
+        else:  # the sum of several calls' COOs, or accumulated into again: the optimizer adds it itself
             m._sgd_pend = None
 
     weight.register_post_accumulate_grad_hook(_post_accumulate)
@@ -306,19 +338,30 @@ class _QuantEmbeddingBase(nn.Module):
         self._ready = None        # grad bits of an exchanged, not yet applied update
         self._counters = None     # host mirror of (now_iteration, iteration_bound, iteration_nt)
         self._rr = None           # ranking range: (bits host int32 [T], bits dev, scale dev) of this step
-        self._ext_rows = []       # rows of the sparse grads handed to an optimizer since the last sync
-                                  # (grad_mode "sparse"; several with gradient accumulation)
+        self._ext_rows = []       # (rows, weight._version then) of the sparse grads handed to an optimizer
+                                  # and not yet known to be synced after its step (grad_mode "sparse";
+                                  # several with gradient accumulation)
         self._sgd_pend = None     # grad_mode "sparse": the last backward's (batch, dy, ...) for the
-                                  # fused optimizer step (_sgd_step_pre_hook)
+                                  # fused optimizer step (_sgd_step_pre_hook); _SEVERAL: see there
+
+    def _take_ext_rows(self) -> torch.Tensor:
+        """The rows to sync now. A COO's rows are forgotten only once the weight has been written
+        since its backward (an optimizer's in-place step moves weight._version), or .grad is gone
+        (stepped and cleared, or discarded): with gradient accumulation a forward that runs before
+        the optimizer's step syncs rows that have not changed yet, and they must be synced again
+        by the first forward after it."""
+        ext = self._ext_rows
+        rows = ext[0][0] if len(ext) == 1 else torch.cat([r for r, _ in ext])
+        w = self.embedding_bag.weight
+        self._ext_rows = [e for e in ext if e[1] == w._version] if w.grad is not None else []
+        return rows
 
     def _sync_external_update(self) -> None:
         """grad_mode "sparse": the optimizer stepped W on the rows of the last COO outside
         libdqrm; bring their maxima (the refreshing forward's full-table scale) and INT4 rows
         up to date before the next forward reads them."""
         if self._ext_rows:
-            rows = self._ext_rows[0] if len(self._ext_rows) == 1 else torch.cat(self._ext_rows)
-            self._tset.rows_changed(rows, repack=self._use_packed(False))
-            self._ext_rows = []
+            self._tset.rows_changed(self._take_ext_rows(), repack=self._use_packed(False))
 
     def _check_errors(self, test_mode: bool) -> None:
         """grad_mode "sparse" / "fused_sgd": flags raised by the previous call's kernels
@@ -367,6 +410,14 @@ class _QuantEmbeddingBase(nn.Module):
             ts.backward_sgd(batch, dy, self.lr, ste=ste, repack=self._use_packed(False), layout=layout)
             return None
         if self.grad_mode == "dp":
+            if self._pending is not None:  # the hooks take one gradient per module: never drop one silently
+                eid = getattr(self, "embedding_id", None)
+                raise RuntimeError(
+                    "%s%s, grad_mode='dp': a second backward reached the module while the gradient of an earlier "
+                    "one is still waiting for its hook call -- grad_update_parallel_comm (then "
+                    "weight_update_parallel_comm), or grad_buffer_update_added_quantization for simulated DP, "
+                    "after every backward; clear_gradients discards it"
+                    % (type(self).__name__, "" if eid is None else " (embedding_id=%s)" % (eid,)))
             self._pending = (batch, dy, ste, layout)
             return None
         return self._sparse_grad(batch, dy, ste, layout)
@@ -379,11 +430,18 @@ class _QuantEmbeddingBase(nn.Module):
         "per_lookup": one STE'd dy row per lookup (set_sparse_grad_form)."""
         rows, vals = self._tset.lookup_grad(batch, dy, ste=ste, layout=layout,
                                             presum=_SPARSE_GRAD_FORM == "presummed")
-        self._ext_rows.append(rows)
+        w = self.embedding_bag.weight
+        self._ext_rows.append((rows, w._version))
         # the fused optimizer step applies this update if the COO reaches a plain SGD step as
-        # the weight's whole gradient (nothing accumulated before it: .grad is None now)
-        self._sgd_pend = (dict(batch=batch, dy=dy, ste=ste, layout=layout, rows=rows, gid=None, gver=None)
-                          if _SGD_HOOK and self.embedding_bag.weight.grad is None else None)
+        # the weight's whole gradient: nothing accumulated before it (.grad is None now), and no
+        # other call of the module in this backward (an entry not yet tied to a grad is one)
+        pend = self._sgd_pend
+        if not _SGD_HOOK or w.grad is not None:
+            self._sgd_pend = None
+        elif pend is _SEVERAL or (pend is not None and pend["gid"] is None):
+            self._sgd_pend = _SEVERAL
+        else:
+            self._sgd_pend = dict(batch=batch, dy=dy, ste=ste, layout=layout, rows=rows, gid=None, gver=None)
         return torch.sparse_coo_tensor(rows.view(1, -1), vals, (self._tset.R, self._tset.D), is_coalesced=False)
 
     def _apply_pending_sgd(self, p: nn.Parameter, lr: float) -> bool:
@@ -393,10 +451,10 @@ class _QuantEmbeddingBase(nn.Module):
         rows kept too), and clear p.grad so the optimizer skips it. Returns whether it did."""
         pend, self._sgd_pend = self._sgd_pend, None
         g = p.grad
-        if (pend is None or g is None or pend["gid"] != id(g) or g._version != pend["gver"]
+        if (not pend or g is None or pend["gid"] != id(g) or g._version != pend["gver"]
                 or self.grad_mode != "sparse"):
             return False
-        self._ext_rows = [r for r in self._ext_rows if r is not pend["rows"]]
+        self._ext_rows = [e for e in self._ext_rows if e[0] is not pend["rows"]]
         self._sync_external_update()  # rows an earlier optimizer step changed, first
         self._tset.backward_sgd(pend["batch"], pend["dy"], lr, ste=pend["ste"], repack=self._use_packed(False),
                                 layout=pend["layout"])
@@ -476,8 +534,7 @@ class QuantEmbeddingBagTwo(_QuantEmbeddingBase):
             refresh_in_fwd = refresh
         changed = None
         if fuse_sync:
-            changed = self._ext_rows[0] if len(self._ext_rows) == 1 else torch.cat(self._ext_rows)
-            self._ext_rows = []
+            changed = self._take_ext_rows()
         y = _EmbeddingFn.apply(self.embedding_bag.weight, self, batch, self.embedding_bit, refresh_in_fwd, fp, "bd",
                                changed)
         if refresh:

@@ -230,7 +230,13 @@ def test_fused_optimizer_step_falls_back_when_grad_changes(dq):
     """The fused optimizer step applies only the COO the last backward produced, as is: a
     gradient accumulated over two backwards, a grad edited in place, or an optimizer with
     another optimizer (Adagrad) get the optimizer's own step on the COO (the module then syncs
-    its |W| maxima)."""
+    its |W| maxima).
+
+    "accumulate": micro-batch 1's gradient carries the table maximum (to twice the old one) into a
+    row that micro-batch 2 does not look up. The forward between the two backwards runs before the
+    optimizer has moved anything, so the rows it syncs must stay on the list for the forward after
+    the step. With both micro-batches random the maximum stayed where it was, in a row neither
+    sync had to see, and forgetting micro-batch 1's rows could not show."""
     from deep_quantized_recommendation_model_dqrm_amd import quant_modules_not_quantize_grad as Q
 
     n, D, B = 300, 16, 256
@@ -238,6 +244,10 @@ def test_fused_optimizer_step_falls_back_when_grad_changes(dq):
     P = [G.pooling_one([n], B, 70 + k)[0] for k in range(2)]
     dy = [G.upstream_grad(1, B, D, 80 + k)[0] for k in range(2)]
     off = torch.arange(B, device="cuda")
+    r = int(np.setdiff1d(P[0], P[1])[0])  # a row of micro-batch 1 only
+    at = np.flatnonzero(P[0] == r)
+    dy_acc = [dy[0].copy(), dy[1]]
+    dy_acc[0][at[0], 0] = (W[r, 0] - 2 * np.abs(W).max()) / 0.1 - dy[0][at[1:], 0].sum()
 
     def step(kind):
         m = _qebt(n, D, W, grad_mode="sparse")
@@ -245,7 +255,8 @@ def test_fused_optimizer_step_falls_back_when_grad_changes(dq):
                else torch.optim.SGD([m.embedding_bag.weight], lr=0.1))
         opt.zero_grad()
         for k in range(2 if kind == "accumulate" else 1):
-            m(torch.from_numpy(P[k]).cuda(), off).backward(torch.from_numpy(dy[k]).cuda())
+            g = dy_acc[k] if kind == "accumulate" else dy[k]
+            m(torch.from_numpy(P[k]).cuda(), off).backward(torch.from_numpy(g).cuda())
         g = m.embedding_bag.weight.grad
         if kind == "scaled":
             g.mul_(0.5)
@@ -260,6 +271,9 @@ def test_fused_optimizer_step_falls_back_when_grad_changes(dq):
         m, got, expect = step(kind)
         torch.testing.assert_close(got, expect, rtol=0, atol=1e-6)
         assert m._sgd_pend is None
+        if kind == "accumulate":  # the maximum now sits in row r, at twice the old one
+            a = got.abs().cpu().numpy()
+            assert a.max(axis=1).argmax() == r and abs(a.max() - 2 * np.abs(W).max()) < 1e-5
         y = m(torch.from_numpy(P[0]).cuda(), off)  # the next forward's scale follows the changed rows
         assert m.eb_scaling_factor.item() == O.table_scale(got.cpu().numpy(), 4)
     m, got, _ = step("adagrad")  # not SGD: the optimizer's own step ran (grad kept)
