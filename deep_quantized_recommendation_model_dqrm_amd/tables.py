@@ -399,13 +399,20 @@ class EmbeddingTableSet:
         if batch.num_tables != self.T:
             raise ValueError("batch has %d tables, set has %d" % (batch.num_tables, self.T))
         B, T, D = batch.num_bags, self.T, self.D
+        shape = (T, B, D) if layout == "tbd" else (B, T, D)
         if out is None:
-            shape = (T, B, D) if layout == "tbd" else (B, T, D)
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
         if layout == "tbd":
             st, sb = B * D, D
         else:
             st, sb = D, T * D
+        if out.dim() == 3 and not out.is_contiguous():
+            # a view into a wider buffer (the interaction's [B, T+1, D'] input): its own strides,
+            # rows of float4 (the kernels store 16 bytes per lane)
+            if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.stride(2) != 1
+                    or out.stride(0) % 4 or out.stride(1) % 4 or out.data_ptr() % 16):
+                raise ValueError("a strided out must be f32 %s, contiguous in D, 16-byte aligned rows" % (shape,))
+            st, sb = (out.stride(0), out.stride(1)) if layout == "tbd" else (out.stride(1), out.stride(0))
         flags = 0
         if refresh_scale:
             flags |= L.DQRM_FWD_REFRESH_SCALE
